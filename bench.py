@@ -11,14 +11,22 @@ the C ABI.  One process per GPU; replicas only (no data-path collective: the pat
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 --master-port P \
         bench.py --gpus N --steps K --warmup W
 
-Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job pairs/s, plus
+Prints ONE JSON line on rank 0 (contract in the task statement): value = whole-job pairs/s, ms_per_step = one timed step, plus
   roofline     -- dominant kernel family = the dense 3x3 dilation-1 forward convs (12 launches per step): several instantiations picked by
                   source count and storage mode (fp32 storage: conv_bf16x3_res / conv_bf16x3_ms / conv_mfma_bf16x3; 16-bit storage: the
                   LDS-DMA kernels conv3x3_h16_dma<NSRC, NRES, format, CP, DIL, IA>, format 1 = bf16, 2 = fp16; the family is DIL = 1); `roofline` aggregates the family and `roofline.kernels` lists each
                   member under the name rocprofv3 gives it; HIP-event timed on the launch stream inside the timed region.
                   roofline_other: the next kernels by time (guided filter, 7x7, 1x1 ...)
-  cpu_baseline -- the CPU oracle (torch fp32 port of the reference) on the host cores, bounded sample, rank 0, N=1 only
   parity       -- which storage mode `value` was measured in and what the committed parity report says about it
+
+A plain run sets up, warms up, times the K steps, writes the last timed step's outputs when `--dump-outputs DIR` is given
+(DIR/<name>.npy, float32, the arrays the timed step returns; inputs and weights are formula-generated, identical from run to run) and
+prints the line.  Everything else moves behind `--full` (off by default), each piece still switchable by its own flag:
+  roofline_other  -- the other kernels by time, from an instrumented pass of the same K steps after the timed region (--graph: the
+                     roofline blocks themselves, from that eager pass)
+  other_storage, two_stream, sustained_value -- the same step in the other storage modes, on two HIP streams, looped >= 3 s (--no-extras)
+  also            -- configs[2]-[4], bounded, in a child process (fusion workload at N=1; --no-also)
+  cpu_baseline    -- the CPU oracle (torch fp32 port of the reference) on the host cores, bounded sample, rank 0, N=1 only (--no-cpu-baseline)
 
 `--storage` (fusion / fusion_seg): since round 5 `value` is measured in the fp16 configuration (`f16`) -- the 16-bit storage mode that meets
 BOTH clauses of SURVEY 8(d) against the reference's own multi-class, near-tie predictions, evaluated (round 6) on THIRTY-TWO 480x640
@@ -73,7 +81,7 @@ def main():
                          "mode).  `value` is then the graph-replay rate; the roofline blocks come from an eager, HIP-event-instrumented pass of "
                          "the same K steps run right after the timed region and say so (`roofline_source`)")
     ap.add_argument("--no-graph", action="store_true",
-                    help="pgd: time the eager step (since round 4 the PGD evaluation step is replayed from one captured hipGraph by default, +3.5 %)")
+                    help="pgd: time the eager step (since round 4 the PGD evaluation step is replayed from one captured hipGraph by default, +3.5 %%)")
     ap.add_argument("--two-stream", action="store_true",
                     help="fusion / fusion_seg: run the timed region itself with ops.CONFIG['two_stream'] = True (the two image streams of the fusion "
                          "network on two HIP streams; bit-identical output, ~+6 %%).  `value` is then the co-scheduled rate and every per-launch "
@@ -108,6 +116,13 @@ def main():
                          "summaries of ONE configuration")
     ap.add_argument("--conv-precision", choices=["f32", "bf16x3"], default="bf16x3",
                     help="arithmetic of the dense convs: exact fp32 MFMA, or split-bf16 (3 bf16 MFMAs, fp32 accumulate)")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure what the headline does not need: roofline_other (and, with --graph, the roofline blocks), the other "
+                         "storage modes, two-stream and sustained rates, the `also` block and the CPU baseline.  Off: set up, warm up, time "
+                         "the K steps, dump, print")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed steps, write what the last timed step returned as DIR/<name>.npy (float32; a fixed, seeded "
+                         "sample when an output is larger than 64 MB in all)")
     args = ap.parse_args()
     if args.attack_precision == "fp32level":
         args.attack_precision = "bf16x6"      # ops.set_attack_precision's name of the same mode
@@ -128,7 +143,7 @@ def main():
         raise SystemExit("--gpus %d but WORLD_SIZE=%d: launch with torch.distributed.run --nproc-per-node %d"
                          % (args.gpus, world, args.gpus))
     also_proc = None
-    if world == 1 and args.workload == "fusion" and not (args.no_also or args.no_extras or args.graph or args.two_stream):
+    if args.full and world == 1 and args.workload == "fusion" and not (args.no_also or args.no_extras or args.graph or args.two_stream):
         # the `also` block (three more workloads, a training step among them) used to run in THIS process before the one JSON
         # line was printed -- a GPU fault there lost the headline.  It now runs in a child process that is started HERE, before this
         # process has made any GPU call (a GPU-initialised process must not start programs on this pool), imports torch and then waits
@@ -295,12 +310,14 @@ def main():
         out = gout
         barrier()
         dt = time.perf_counter() - t0
-        timer = ops.KernelTimer(lambda tag: True)
-        ops.TIMER = timer              # the instrumented eager pass (not part of `value`)
-        for _ in range(args.steps):
-            step()
-        torch.cuda.synchronize()
-        ops.TIMER = None
+        dumped = host_outputs(args.workload, out) if args.dump_outputs else None
+        if args.full:
+            timer = ops.KernelTimer(lambda tag: True)
+            ops.TIMER = timer              # the instrumented eager pass (not part of `value`)
+            for _ in range(args.steps):
+                step()
+            torch.cuda.synchronize()
+            ops.TIMER = None
     else:
         barrier()
         ops.TIMER = timer
@@ -310,7 +327,8 @@ def main():
         barrier()
         dt = time.perf_counter() - t0
         ops.TIMER = None
-        if DOM_PRIOR:
+        dumped = host_outputs(args.workload, out) if args.dump_outputs else None
+        if DOM_PRIOR and args.full:
             timer_all = ops.KernelTimer(lambda tag: True)
             ops.TIMER = timer_all
             for _ in range(args.steps):
@@ -318,13 +336,15 @@ def main():
             torch.cuda.synchronize()
             ops.TIMER = None
     assert torch.isfinite(out).all()
+    if dumped is not None:
+        write_outputs(dumped, args.dump_outputs, "" if world == 1 else "_rank%d" % rank)
     from paif_amd.dist_utils import max_over_ranks
     dt = max_over_ranks(dt, dist, dev)
     # sustained pass: the K timed steps above last ~0.15 s on the headline workload -- a burst right after an
     # idle period, the most favourable thermal / power state.  The same step is then looped for >= --sustain-seconds (default 3 s)
     # and reported as `sustained_value`; `value` stays the contract's K-step figure.
     other_storage = []
-    if args.workload in ("fusion", "fusion_seg") and not args.graph and not args.no_extras:
+    if args.full and args.workload in ("fusion", "fusion_seg") and not args.graph and not args.no_extras:
         for mode in ops.STORAGE_MODES:
             if mode == args.storage:
                 continue
@@ -339,7 +359,7 @@ def main():
             other_storage.append((mode, max_over_ranks(time.perf_counter() - t2, dist, dev)))
         ops.set_storage(args.storage)
     two_stream = None
-    if args.workload in ("fusion", "fusion_seg") and not args.graph and not args.two_stream and not args.no_extras:
+    if args.full and args.workload in ("fusion", "fusion_seg") and not args.graph and not args.two_stream and not args.no_extras:
         # the same K steps with the two image streams of the fusion network on two HIP streams (ops.CONFIG["two_stream"]): identical
         # results, kernels of one stream fill the CUs the other's launches leave idle.  Reported beside `value`, not as it: per-launch
         # durations under co-scheduling measure CU sharing, so the roofline blocks (and the rocprofv3 summary they must agree with) are
@@ -355,7 +375,7 @@ def main():
         two_stream = max_over_ranks(time.perf_counter() - t3, dist, dev)
         ops.CONFIG["two_stream"] = False
     sustained = None
-    if args.sustain_seconds > 0 and not args.graph and not args.no_extras:
+    if args.full and args.sustain_seconds > 0 and not args.graph and not args.no_extras:
         n_s = int(args.sustain_seconds / max(dt / args.steps, 1e-6)) + 1
         barrier()
         t1 = time.perf_counter()
@@ -384,10 +404,12 @@ def main():
             a_ = summ.get(f, (0, 0.0, 0, 0))
             summ[f] = (a_[0] + n_, a_[1] + ms_, a_[2] + fl_, a_[3] + by_)
             members.setdefault(f, []).append(tag)
-        if args.workload != "fusion":       # the segmentation workloads: the kernel with the largest share of the timed region
+        if not summ:                         # nothing instrumented ran: a plain --graph run (its eager pass is --full's)
+            DOM = None
+        elif args.workload != "fusion":       # the segmentation workloads: the kernel with the largest share of the timed region
             DOM = max(summ, key=lambda k: summ[k][1])
         else:
-            DOM = DOMINANT
+            DOM = DOMINANT if DOMINANT in summ else max(summ, key=lambda k: summ[k][1])
 
         def roof_block(tag):
             n_, ms_, fl_, by_ = summ[tag]
@@ -450,7 +472,7 @@ def main():
                                   for k in sorted(members[tag], key=lambda k: -per_kernel[k][1])]
             return blk
 
-        roof = roof_block(DOM)
+        roof = roof_block(DOM) if DOM is not None else None
         # PMC counters cannot be read live: `traffic` comes from the committed rocprofv3 --pmc summary of this same command
         # (profiles/pmc_traffic.json, one section per workload / storage), and the line says when that summary was measured on
         # different kernel sources
@@ -499,11 +521,12 @@ def main():
                 kk["traffic"] = pmc_lookup(kk["kernel"])
             return blk
 
-        add_traffic(roof)
-        roof["traffic_source"] = ("profiles/pmc_traffic.json[%s]: rocprofv3 --pmc passes of this same command run by the builder "
-                                  "(tools/pmc_run.sh + tools/pmc_traffic.py); PMC counters cannot be read inside an un-profiled run" % wkey)
-        if traffic_note:
-            roof["traffic_note"] = traffic_note
+        if roof is not None:
+            add_traffic(roof)
+            roof["traffic_source"] = ("profiles/pmc_traffic.json[%s]: rocprofv3 --pmc passes of this same command run by the builder "
+                                      "(tools/pmc_run.sh + tools/pmc_traffic.py); PMC counters cannot be read inside an un-profiled run" % wkey)
+            if traffic_note:
+                roof["traffic_note"] = traffic_note
         others = [add_traffic(roof_block(k)) for k in sorted(summ, key=lambda k: -summ[k][1]) if k != DOM][:4]
         res = {
             "metric": "fused image-pairs/sec at 480x640 bs=%d per GPU (%s)" % (bpg, {"fusion": "fusion-net forward", "fusion_seg": "fusion + SegFormer forward", "pgd": "PGD-10 adversarial eval", "train": "adversarial-training step"}[args.workload]),
@@ -555,7 +578,8 @@ def main():
             res["parity"] = parity_block(args.storage)
         if args.graph:
             res["mode"] = "hipGraph replay (one captured graph per step)"
-            res["roofline_source"] = "eager HIP-event pass of the same %d steps after the timed region" % args.steps
+            res["roofline_source"] = ("eager HIP-event pass of the same %d steps after the timed region" % args.steps if args.full else
+                                      "not measured: the eager HIP-event pass after the timed region runs under --full")
         elif timer_all is not None:
             res["roofline_source"] = ("`roofline`%s: HIP events around every launch of that kernel INSIDE the timed region; `roofline_other`: an "
                                       "instrumented pass of the same %d steps right after it" % (
@@ -598,7 +622,7 @@ def main():
             except Exception as e:                 # timeout, broken pipe, bad JSON: the headline line survives
                 also_proc.kill()
                 res["also"] = {"error": "%s: %s" % (type(e).__name__, e)}
-        if world == 1 and not args.no_cpu_baseline and args.workload in ("fusion", "fusion_seg", "pgd"):
+        if args.full and world == 1 and not args.no_cpu_baseline and args.workload in ("fusion", "fusion_seg", "pgd"):
             # BASELINE.md 3b's protocol (3 warm-up + 5 timed forwards, at B=1 and at B=8) whenever the run is a full-length one
             # (--steps >= 20, the default); shorter runs take the bounded sample
             res["cpu_baseline"] = cpu_baseline(args.workload, ir_np, vis_np, lab_np, args.cpu_baseline_full or args.steps >= 20, args.backbone)
@@ -813,6 +837,34 @@ def self_launch(n):
         print("bench.py: the ranks exited 0 but rank 0 printed no JSON line", file=sys.stderr)
         rc = 1
     return rc
+
+
+DUMP_LIMIT_BYTES = 64 << 20
+
+
+def host_outputs(workload, out):
+    """What the timed step returned, copied to the host right after the timed region: name -> float32 array (float64 kept)."""
+    name = {"fusion": "fused", "fusion_seg": "seg_logits", "pgd": "seg_logits", "train": "loss"}[workload]
+    a = out.detach()
+    a = a.cpu() if a.dtype == torch.float64 else a.float().cpu()
+    return {name: a.numpy()}
+
+
+def write_outputs(arrays, out_dir, suffix=""):
+    """`--dump-outputs`: each array as <out_dir>/<name><suffix>.npy.  When the arrays hold more than 64 MB in all, each is replaced by
+    the same fixed, seeded sample of its flattened elements (<name><suffix>.npy), and <name>_index<suffix>.npy (float64) holds the
+    positions of the sample."""
+    import numpy as np
+
+    os.makedirs(out_dir, exist_ok=True)
+    total = sum(a.nbytes for a in arrays.values())
+    for name, a in arrays.items():
+        if total > DUMP_LIMIT_BYTES:
+            k = max(1, int(a.size * DUMP_LIMIT_BYTES / (total * (1 + 8 / a.itemsize))))     # sample + its float64 positions fit the limit
+            idx = np.sort(np.random.default_rng(20261016).choice(a.size, size=min(k, a.size), replace=False))
+            np.save(os.path.join(out_dir, "%s_index%s.npy" % (name, suffix)), idx.astype(np.float64))
+            a = np.ascontiguousarray(a).reshape(-1)[idx]
+        np.save(os.path.join(out_dir, name + suffix + ".npy"), a)
 
 
 # MFMAs per product by kernel storage code (paif_common.h; the kernels' last / fourth template argument): fp32 maps 3; bf16 maps 2; plain

@@ -9,8 +9,8 @@ fails loudly when its HIP library is missing.
 Pinning status
 --------------
 * Pinned against the reference ITSELF, imported in the build container with oracle/shims
-  (oracle/make_golden.py -> tests/golden/*.npz; tests/test_oracle_golden.py, and live in
-  tests/test_oracle_vs_reference.py when /root/reference is present).  The reference has no
+  (oracle/make_golden.py -> tests/golden/*.npz; tests/test_oracle_golden.py, and on ragged
+  sizes in tests/test_oracle_vs_reference.py via oracle/make_golden_standalone.py).  The reference has no
   tests, golden vectors or fixtures of its own.
 * PARITY UNPINNED at four third-party boundaries whose source is not under /root/reference
   and whose packages are not installable here: guided_filter_pytorch.GuidedFilter (version

@@ -1,7 +1,7 @@
 """Input pipeline: paif_amd.TaskFusion_dataset2 against the reference's class on a
-directory of synthetic PNGs (the reference is imported when /root/reference is present; cv2 comes from oracle/shims)."""
+directory of synthetic PNGs (the reference's items on that set are stored in tests/golden/gs_dataset_items.npz, written by
+oracle/make_golden_standalone.py)."""
 import os
-import sys
 
 import numpy as np
 import pytest
@@ -11,7 +11,7 @@ from PIL import Image
 from paif_amd import synthetic as S
 from paif_amd.TaskFusion_dataset2 import Fusion_dataset, prepare_data_path, imread_gray
 
-REF = "/root/reference"
+GOLDEN = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden")
 
 
 def _write_set(root, n=3, H=48, W=64, colour_ir=False):
@@ -52,21 +52,13 @@ def test_grey_read_of_colour_file_uses_opencv_weights(tmp_path):
     assert imread_gray(p).tolist() == [[76, 150, 29, 124]]     # cv2.cvtColor(..., COLOR_BGR2GRAY) on these pixels
 
 
-@pytest.mark.skipif(not os.path.isdir(REF), reason="reference tree not present")
 @pytest.mark.parametrize("colour_ir", [False, True])
 def test_matches_reference_class(tmp_path, colour_ir):
     irp, vip, lbp = _write_set(str(tmp_path), colour_ir=colour_ir)
-    shims = os.path.join(os.path.dirname(os.path.dirname(os.path.abspath(__file__))), "oracle", "shims")
-    sys.path[:0] = [shims, REF]
-    try:
-        sys.modules.pop("TaskFusion_dataset2", None)
-        import TaskFusion_dataset2 as R
-        ref = R.Fusion_dataset('val', ir_path=irp, vi_path=vip, label_path=lbp)
-    finally:
-        sys.path.remove(shims)
-        sys.path.remove(REF)
-        sys.modules.pop("TaskFusion_dataset2", None)
-        sys.modules.pop("cv2", None)
+    g = np.load(os.path.join(GOLDEN, "gs_dataset_items.npz"))
+    tag = "colour" if colour_ir else "grey"
+    ref = [(torch.from_numpy(g[tag + "_vis"][i]), torch.from_numpy(g[tag + "_ir"][i]), torch.from_numpy(g[tag + "_label"][i]),
+            str(g[tag + "_name"][i])) for i in range(len(g[tag + "_name"]))]
     mine = Fusion_dataset('val', ir_path=irp, vi_path=vip, label_path=lbp)
     assert len(mine) == len(ref)
     for i in range(len(ref)):
