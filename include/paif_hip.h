@@ -751,6 +751,36 @@ int paif_adamw_step(float* p, const float* g, float* m, float* v, const unsigned
                     const float* group_decay, const float* group_step_size, float one_minus_beta1, float beta2, float one_minus_beta2,
                     float bc2_sqrt, float eps, paif_stream_t stream);
 
+/* ReCoNet baseline (fusion_model/Reconet.py of the reference; csrc/reconet.hip).  All planes fp32 [B,H,W]; i1 / i2 are addressed as
+ * plane b at i1 + b * sb1 (floats), so a channel slice of a [B,C,H,W] tensor needs no copy; every other plane is dense.
+ * pack: paif_reconet_pack_floats(dim) floats, written by one paif_reconet_pack_head and three paif_reconet_pack_group calls.
+ * dim 16, 32 or 64 (PAIF_ENOSUP otherwise).  No host synchronisation, no allocation: capturable. */
+size_t paif_reconet_pack_floats(int dim);
+/* fusion_model/Reconet.py:10-23, :33-43: conv_d[group] = Conv2d(3, dim, 3, dilation group + 1) [+ eval-mode BatchNorm2d, folded here:
+ * bn_gamma .. bn_var all null without it] and this group's dim rows of conv_s.0.weight [1, 3*dim, 3, 3] (w_s: the whole tensor). */
+int paif_reconet_pack_group(const float* w, const float* b, const float* bn_gamma, const float* bn_beta, const float* bn_mean,
+                            const float* bn_var, float bn_eps, const float* w_s, int dim, int group, float* pack, paif_stream_t stream);
+/* fusion_model/Reconet.py:61-62 (att_a_conv / att_b_conv weights [1,2,3,3]), :39-43 (conv_s bias). */
+int paif_reconet_pack_head(const float* att_a_w, const float* att_b_w, const float* b_s, float* pack, paif_stream_t stream);
+/* fusion_model/Reconet.py:71: i_f[0] = max(i_1, i_2) (use_max) or (i_1 + i_2) / 2. */
+int paif_reconet_init(const float* i1, size_t sb1, const float* i2, size_t sb2, int use_max, float* out, int B, int H, int W,
+                      paif_stream_t stream);
+/* Reverse of fusion_model/Reconet.py:71: d_i1 += route * d_f0, d_i2 += (1 - route) * d_f0; the elementwise max splits a tie 0.5 / 0.5. */
+int paif_reconet_init_bwd(const float* i1, size_t sb1, const float* i2, size_t sb2, int use_max, const float* d_f0, float* d_i1,
+                          float* d_i2, int B, int H, int W, paif_stream_t stream);
+/* fusion_model/Reconet.py:82-105 (_sub_forward, _attention) with :45-52 (DGroup.forward): one recurrence f_prev -> f_next as ONE
+ * launch; the 3*dim-channel map stays in registers.  att_a / att_b (optional, both or none): the two attention maps (show_detail,
+ * and the reverse pass's tape).  f_next must not alias f_prev. */
+int paif_reconet_step_fwd(const float* i1, size_t sb1, const float* i2, size_t sb2, const float* f_prev, const float* pack, int dim,
+                          float* f_next, float* att_a, float* att_b, int B, int H, int W, paif_stream_t stream);
+/* Reverse of one recurrence (input gradients; fusion_model/Reconet.py:82-105 backwards): from d_f_next and the taped planes f_prev,
+ * att_a, att_b, f_next (the pre-GELU values are recomputed) -> d_f_prev (written), d_i1 / d_i2 (accumulate != 0: added to, else
+ * written).  The channel max of the attention input routes a tie to the image plane (index 0 of the reference's cat).
+ * workspace: 2 * B*H*W floats.  d_f_prev must not alias d_f_next.  Bit-reproducible (no atomics). */
+int paif_reconet_step_bwd(const float* i1, size_t sb1, const float* i2, size_t sb2, const float* f_prev, const float* att_a,
+                          const float* att_b, const float* f_next, const float* d_f_next, const float* pack, int dim, float* d_i1,
+                          float* d_i2, float* d_f_prev, float* workspace, int accumulate, int B, int H, int W, paif_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

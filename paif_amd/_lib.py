@@ -199,6 +199,13 @@ SIGNATURES = {
     "paif_rowscale_add_fwd": (c_int, [F, F, F, F, c_int, c_size_t, c_int, c_int, F]),
     "paif_adamw_step": (c_int, [F, F, F, F, F, c_size_t, c_int, POINTER(c_float), POINTER(c_float), c_float, c_float, c_float, c_float,
                                 c_float, F]),
+    "paif_reconet_pack_floats": (c_size_t, [c_int]),
+    "paif_reconet_pack_group": (c_int, [F, F, F, F, F, F, c_float, F, c_int, c_int, F, F]),
+    "paif_reconet_pack_head": (c_int, [F, F, F, F, F]),
+    "paif_reconet_init": (c_int, [F, c_size_t, F, c_size_t, c_int, F, c_int, c_int, c_int, F]),
+    "paif_reconet_init_bwd": (c_int, [F, c_size_t, F, c_size_t, c_int, F, F, F, c_int, c_int, c_int, F]),
+    "paif_reconet_step_fwd": (c_int, [F, c_size_t, F, c_size_t, F, F, c_int, F, F, F, c_int, c_int, c_int, F]),
+    "paif_reconet_step_bwd": (c_int, [F, c_size_t, F, c_size_t, F, F, F, F, F, F, c_int, F, F, F, F, c_int, c_int, c_int, c_int, F]),
 }
 
 _lib = None

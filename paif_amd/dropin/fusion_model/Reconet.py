@@ -1,5 +1,2 @@
-class ReCoNet:
-    """reference fusion_model/Reconet.py (ReCoNet baseline): imported at test_original.py:19, never constructed."""
-
-    def __init__(self, *args, **kwargs):
-        raise NotImplementedError("fusion_model.Reconet.ReCoNet is a competitor baseline, out of scope for paif_amd (SURVEY.md section 2)")
+"""`from fusion_model.Reconet import ReCoNet` (reference test_original.py:19): the MI355X-native baseline."""
+from paif_amd.fusion_model.reconet import ConvGroup, DGroup, ReCoNet  # noqa: F401

@@ -2135,3 +2135,76 @@ def spa1_bwd(dout, u, o, s, w, k, prelu, want_dpre=False):
     _lib.check(lib().paif_spa1_bwd_input(_p(dout), _p(u), _p(o), _p(s), _p(w.detach().contiguous()), k, _p(prelu), _p(dpre), _p(d_o), _p(d_r),
                                          B, H, W, _stream()), "spa1_bwd")
     return (d_o, d_r, dpre) if want_dpre else (d_o, d_r)
+
+
+# ---------------------------------------------------------------------------------------------
+# ReCoNet baseline (csrc/reconet.hip; fusion_model/reconet.py is the module)
+# ---------------------------------------------------------------------------------------------
+def _plane(t):
+    """([B,1,H,W] fp32 device view whose planes are dense) -> (pointer, batch stride in floats): a channel slice of a dense
+    [B,C,H,W] tensor is passed as it is, anything else is made dense first."""
+    if not t.is_cuda:
+        raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor -- there is no CPU path" % t.device)
+    if t.dtype != torch.float32:
+        raise TypeError("expected float32, got %s" % t.dtype)
+    B, C, H, W = t.shape
+    assert C == 1, "a 1-channel plane is expected, got %d channels" % C
+    if not ((W == 1 or t.stride(3) == 1) and (H == 1 or t.stride(2) == W) and (B == 1 or t.stride(0) >= H * W)):
+        t = t.contiguous()
+    return t, ctypes.c_void_p(t.data_ptr()), (t.stride(0) if B > 1 else H * W)
+
+
+def reconet_pack(att_a_w, att_b_w, groups, w_s, b_s, dim):
+    """groups: three (conv weight [dim,3,3,3], conv bias, bn) with bn = None or (gamma, beta, running_mean, running_var, eps)
+    -> the kernels' weight layout (eval-mode BatchNorm folded into weight and bias)."""
+    dev = w_s.device
+    pack = torch.empty(lib().paif_reconet_pack_floats(dim), device=dev, dtype=torch.float32)
+    c = lambda t: t.detach().contiguous()
+    ws = c(w_s)
+    _lib.check(lib().paif_reconet_pack_head(_p(c(att_a_w)), _p(c(att_b_w)), _p(c(b_s)), _p(pack), _stream()), "reconet_pack_head")
+    for g, (w, b, bn) in enumerate(groups):
+        ga, be, mu, var, eps = (c(bn[0]), c(bn[1]), c(bn[2]), c(bn[3]), bn[4]) if bn is not None else (None, None, None, None, 0.0)
+        _lib.check(lib().paif_reconet_pack_group(_p(c(w)), _p(c(b)), _p(ga), _p(be), _p(mu), _p(var), eps, _p(ws), dim, g, _p(pack), _stream()),
+                   "reconet_pack_group")
+    return pack
+
+
+def reconet_init(i1, i2, use_max):
+    B, _, H, W = i1.shape
+    i1, p1, s1 = _plane(i1)
+    i2, p2, s2 = _plane(i2)
+    out = torch.empty((B, 1, H, W), device=i1.device, dtype=torch.float32)
+    _lib.check(lib().paif_reconet_init(p1, s1, p2, s2, int(use_max), _p(out), B, H, W, _stream()), "reconet_init")
+    return out
+
+
+def reconet_init_bwd_(d_i1, d_i2, i1, i2, use_max, d_f0):
+    """d_i1, d_i2 += the initialisation's share of d_f0 (in place)."""
+    B, _, H, W = i1.shape
+    i1, p1, s1 = _plane(i1)
+    i2, p2, s2 = _plane(i2)
+    _lib.check(lib().paif_reconet_init_bwd(p1, s1, p2, s2, int(use_max), _p(d_f0), _p(d_i1), _p(d_i2), B, H, W, _stream()), "reconet_init_bwd")
+
+
+def reconet_step(i1, i2, f_prev, pack, dim, want_att=False):
+    """One recurrence: -> f_next, or (f_next, att_a, att_b)."""
+    B, _, H, W = i1.shape
+    i1, p1, s1 = _plane(i1)
+    i2, p2, s2 = _plane(i2)
+    f_next = torch.empty((B, 1, H, W), device=i1.device, dtype=torch.float32)
+    att_a = torch.empty_like(f_next) if want_att else None
+    att_b = torch.empty_like(f_next) if want_att else None
+    _lib.check(lib().paif_reconet_step_fwd(p1, s1, p2, s2, _p(f_prev), _p(pack), dim, _p(f_next), _p(att_a), _p(att_b), B, H, W, _stream()),
+               "reconet_step_fwd")
+    return (f_next, att_a, att_b) if want_att else f_next
+
+
+def reconet_step_bwd(i1, i2, f_prev, att_a, att_b, f_next, d_f_next, pack, dim, d_i1, d_i2, workspace, accumulate):
+    """Reverse of one recurrence: d_i1, d_i2 written (accumulate False) or added to, -> d_f_prev."""
+    B, _, H, W = i1.shape
+    i1, p1, s1 = _plane(i1)
+    i2, p2, s2 = _plane(i2)
+    d_f_prev = torch.empty((B, 1, H, W), device=i1.device, dtype=torch.float32)
+    _lib.check(lib().paif_reconet_step_bwd(p1, s1, p2, s2, _p(f_prev), _p(att_a), _p(att_b), _p(f_next), _p(d_f_next), _p(pack), dim, _p(d_i1), _p(d_i2),
+                                           _p(d_f_prev), _p(workspace), int(accumulate), B, H, W, _stream()), "reconet_step_bwd")
+    return d_f_prev
