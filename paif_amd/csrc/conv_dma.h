@@ -1,4 +1,4 @@
-// Interface between the dense-conv dispatcher (conv_mfma.hip) and the LDS-DMA 3x3 kernel (conv_dma.hip).
+// Interface between the dense-conv dispatcher (conv_mfma.hip) and the LDS-DMA kernels (conv_dma.hip: 3x3, 7x7; conv_dma_1x1.hip: 1x1).
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -29,5 +29,10 @@ bool eligible7(int nsrc, int nres, int B, int H, int W, float alpha);   // the 7
 bool eligible_d2(int nsrc, int nres, int B, int H, int W, float alpha);  // 3x3 dilation 2 behind an input ReLU: one source, 1 or 3 residual maps
 bool can_cpool(int nsrc, int nres, int kh, int cout, int dil);   // the instantiations that write Args::cpool
 int launch(const Args& a, hipStream_t st);
+
+// conv_dma_1x1.hip: the 1x1 over three 32-channel sources without residual maps (the folded decomposition conv) as a streaming kernel;
+// launch() hands it every Args with kh == 1.  Switch: PAIF_CONV_DMA1X1=0 (read once).
+bool eligible_1x1(int nsrc, int nres, int B, int H, int W);
+int launch_1x1(const Args& a, hipStream_t st);
 
 }  // namespace paif_conv_dma

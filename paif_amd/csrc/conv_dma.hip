@@ -794,6 +794,7 @@ int launch(const Args& a, hipStream_t st) {
     return PAIF_ENOSUP;
   }
   if (a.kh == 7) return launch_7(a, st);
+  if (a.kh == 1) return launch_1x1(a, st);
   if (a.dil == 2) {
     if (a.nsrc == 1 && a.in_relu && a.nres == 1) return a.cpool ? launch_d2<1, true>(a, st) : launch_d2<1, false>(a, st);
     if (a.nsrc == 1 && a.in_relu && a.nres == 3) return a.cpool ? launch_d2<3, true>(a, st) : launch_d2<3, false>(a, st);

@@ -1698,6 +1698,11 @@ static inline ConvVariant bf16x3_variant(const ConvArgs& a, int kh, int dil) {
   if (kh == 3 && dil == 2 && st_h16(a) && a.wl0 && a.in_act == 2 && !a.pool_partial && a.cout == 32 &&
       paif_conv_dma::eligible_d2(a.nsrc, res_count(a), a.B, a.H, a.W, a.alpha))
     return CV_DMA;
+  // the folded decomposition 1x1 (three 16-bit sources, plain 16-bit weights, no residual maps), from the tile count at which the
+  // persistent form is taken: the streaming LDS-DMA kernel (conv_dma_1x1.hip)
+  if (kh == 1 && dil == 1 && st_h16(a) && a.wl0 && a.in_act == 0 && !a.pool_partial && a.cout == 32 && ws_eligible(a) &&
+      paif_conv_dma::eligible_1x1(a.nsrc, res_count(a), a.B, a.H, a.W))
+    return CV_DMA;
   if (takes_ws(a, kh, dil)) return CV_WS;
   if (kh == 3 && dil == 1 && !st_is_f16(a)) {    // (fp16 maps: LDS-DMA, persistent or tile-per-workgroup kernel only)
     if (res_eligible(a)) return CV_RES;
@@ -2095,6 +2100,7 @@ int paif_conv2d_kernel_name(const paif_conv_desc* d, int B, int H, int W, char* 
   switch (bf16x3_variant(a, d->kh, d->dil)) {
     case CV_DMA:
       if (d->kh == 7) snprintf(buf, buflen, "conv7x7_h16_dma<%d>", a.st >= 3 ? 2 : 1);
+      else if (d->kh == 1) snprintf(buf, buflen, "conv_h16_dma_1x1<%d>", a.st >= 3 ? 2 : 1);
       else snprintf(buf, buflen, "conv3x3_h16_dma<%d, %d, %d, %s, %d, %d>", d->nsrc, res_count(a), a.st >= 3 ? 2 : 1, d->cpool ? "true" : "false",
                     d->dil, d->dil == 2 ? 2 : 0);
       break;
