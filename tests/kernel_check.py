@@ -51,6 +51,24 @@ def pw(name, got, ref):
     err(name, got, ref, PW * max(1.0, float(ref.detach().abs().max())))
 
 
+def h16(name, got, ref, eps16, bound32, keep=None):
+    """A 16-bit stored output (tests/test_forward_kernels_gpu.py), per element:
+    |got - ref| <= 1.01 * eps16 * |ref| + bound32, eps16 = 2^-8 (bf16) or 2^-11 (fp16) for the rounding of the stored value
+    and bound32 the bound the fp32 form of the same kernel has at that case.  Prints the element that comes closest to (or
+    exceeds by most) its own bound."""
+    got, ref = got.detach().float().cpu().double(), ref.detach().double()
+    assert got.shape == ref.shape, (name, tuple(got.shape), tuple(ref.shape))
+    assert bool(torch.isfinite(got).all()), name
+    d, tol = (got - ref).abs(), 1.01 * eps16 * ref.abs() + bound32
+    if keep is not None:
+        d, tol = d[keep], tol[keep]
+    d, tol = d.reshape(-1), tol.reshape(-1)
+    i = int(torch.where(d > tol, d - tol + 1.0, d / tol.clamp_min(1e-300)).argmax())     # an element over its bound, else the closest
+    e, b = float(d[i]), float(tol[i])
+    print("ERR | %s | %.3e | %.3e" % (name, e, b))
+    assert bool((d <= tol).all()), (name, e, b)
+
+
 def exact(name, got, ref):
     got = got.cpu()
     assert got.shape == ref.shape and got.dtype == ref.dtype, (name, tuple(got.shape), tuple(ref.shape))
