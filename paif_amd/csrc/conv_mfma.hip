@@ -1684,7 +1684,7 @@ static inline bool takes_ws(const ConvArgs& a, int kh, int dil) {
 }
 
 // which split-bf16 kernel a launch takes (one place: the dispatcher and paif_conv2d_kernel_name use it)
-enum ConvVariant { CV_PLAIN, CV_HOOKS, CV_WS, CV_RES, CV_MS, CV_DMA };
+enum ConvVariant { CV_PLAIN, CV_HOOKS, CV_WS, CV_RES, CV_MS, CV_DMA, CV_ROWS };
 static inline int res_count(const ConvArgs& a) { return a.res[0] ? (a.res[1] ? (a.res[2] ? 3 : 2) : 1) : 0; }
 static inline ConvVariant bf16x3_variant(const ConvArgs& a, int kh, int dil) {
   if (needs_hooks(a)) return CV_HOOKS;
@@ -1694,6 +1694,11 @@ static inline ConvVariant bf16x3_variant(const ConvArgs& a, int kh, int dil) {
        (kh == 3 && a.cout == 16 && paif_conv_dma::eligible16(a.nsrc, res_count(a), a.B, a.H, a.W, a.alpha)) ||
        (kh == 7 && a.cout == 32 && paif_conv_dma::eligible7(a.nsrc, res_count(a), a.B, a.H, a.W, a.alpha))))
     return CV_DMA;
+  // 3x3 dilation 2 without an input activation (the ResidualModule's composed conv), 16-bit source, 16-bit or fp32 output, one source,
+  // large maps: the row-streaming LDS-DMA kernel (conv_dma_rows.hip).  A launch with a fused ChannelPool stays on the persistent form.
+  if (kh == 3 && dil == 2 && (st_h16(a) || a.st == 4) && a.wl0 && a.in_act == 0 && !a.pool_partial && !a.cpool && a.cout == 32 &&
+      paif_conv_dma::eligible_rows(a.nsrc, res_count(a), 0, 0, st_is_f16(a) ? 1 : 0, a.st == 4 ? 1 : 0, a.B, a.H, a.W))
+    return CV_ROWS;
   // round 6: 3x3 dilation 2 behind an input ReLU (the composed DilConv), 16-bit maps in and out, one source, 1 or 3 residual maps
   if (kh == 3 && dil == 2 && st_h16(a) && a.wl0 && a.in_act == 2 && !a.pool_partial && a.cout == 32 &&
       paif_conv_dma::eligible_d2(a.nsrc, res_count(a), a.B, a.H, a.W, a.alpha))
@@ -1718,12 +1723,14 @@ static inline ConvVariant bf16x3_variant(const ConvArgs& a, int kh, int dil) {
 static inline bool variant_can_cpool(const ConvArgs& a, int kh, int dil) {
   if (a.cout != 32 || needs_hooks(a)) return false;
   if (bf16x3_variant(a, kh, dil) == CV_DMA) return paif_conv_dma::can_cpool(a.nsrc, res_count(a), kh, a.cout, dil);
-  return true;
+  return true;   // (CV_ROWS has no pool: the launch that carries one takes the persistent form, which has)
 }
 
 template <int KH, int DIL, int ST>
 int launch_bf16x3_st(const ConvArgs& a, hipStream_t st) {
-  switch (bf16x3_variant(a, KH, DIL)) {
+  const ConvVariant cv = bf16x3_variant(a, KH, DIL);
+  switch (cv) {
+    case CV_ROWS:
     case CV_DMA: {
       paif_conv_dma::Args d{};
       for (int s = 0; s < 3; ++s) { d.src[s] = a.src[s]; d.res[s] = a.res[s]; }
@@ -1732,7 +1739,8 @@ int launch_bf16x3_st(const ConvArgs& a, hipStream_t st) {
       d.f16 = paif::st_f16(ST) ? 1 : 0;
       d.cpool = a.cpool;
       d.dil = DIL; d.in_relu = a.in_act == 2 ? 1 : 0;
-      return paif_conv_dma::launch(d, st);
+      d.out_f32 = paif::st_out(ST) == 0 ? 1 : 0;
+      return cv == CV_ROWS ? paif_conv_dma::launch_rows(d, st) : paif_conv_dma::launch(d, st);
     }
     case CV_HOOKS:
       if constexpr (ST == 0) return launch_bf16x3_h<KH, DIL, true>(a, st);
@@ -2079,6 +2087,7 @@ int paif_conv2d_kernel_name(const paif_conv_desc* d, int B, int H, int W, char* 
   a.B = B; a.H = H; a.W = W;
   a.nblk = B * ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
   a.st = d->storage; a.wl0 = (d->precision == PAIF_CONV_BF16 || d->precision == PAIF_CONV_F16) ? 1 : 0; a.alpha = d->alpha;
+  a.cpool = d->cpool;
   const int code = kernel_st(a);
   if (d->precision == PAIF_CONV_BF16X6 && d->cin == 32) {
     snprintf(buf, buflen, "conv_mfma_bf16x6<%d, %d, %s, 0>", d->kh, d->dil, needs_hooks(a) ? "true" : "false");
@@ -2104,6 +2113,7 @@ int paif_conv2d_kernel_name(const paif_conv_desc* d, int B, int H, int W, char* 
       else snprintf(buf, buflen, "conv3x3_h16_dma<%d, %d, %d, %s, %d, %d>", d->nsrc, res_count(a), a.st >= 3 ? 2 : 1, d->cpool ? "true" : "false",
                     d->dil, d->dil == 2 ? 2 : 0);
       break;
+    case CV_ROWS: snprintf(buf, buflen, "conv3x3_h16_dma_rows<%d, %d, %s>", a.st >= 3 ? 2 : 1, res_count(a), a.st == 4 ? "true" : "false"); break;
     case CV_WS: snprintf(buf, buflen, "conv_bf16x3_ws%s<%d, %d, %d>", d->in_act == 2 ? "r" : "", d->kh, d->dil, code); break;
     case CV_RES: snprintf(buf, buflen, "conv_bf16x3_res<%d, %d, %d, %d, %d>", d->kh, d->dil, d->nsrc, PAIF_RES_ROWS, code); break;
     case CV_MS: snprintf(buf, buflen, "conv_bf16x3_ms<%d, %d, %d, %d>", d->kh, d->dil, d->nsrc, code); break;
