@@ -233,13 +233,20 @@ int paif_conv2d_can_cpool(const paif_conv_desc* d, int B, int H, int W);
 int paif_channel_pool1_fwd(const float* x, float* comp_off, int B, int H, int W, paif_stream_t stream);
 int paif_channel_pool1_fwd_bf16(const float* x, float* comp_off, int B, int H, int W, paif_stream_t stream);
 int paif_channel_pool1_fwd_f16(const float* x, float* comp_off, int B, int H, int W, paif_stream_t stream);
-/* 1 if paif_conv2d_fwd would run this descriptor on the persistent wave-specialised kernel (conv_bf16x3_ws),
- * 0 for the tile-per-workgroup kernel (conv_mfma_*): lets a profiler-side caller name the kernel it times. */
+/* 1 if paif_conv2d_fwd would run this descriptor on the persistent wave-specialised kernel (conv_bf16x3_ws / conv_bf16x3_wsr),
+ * 0 for every other kernel: the same decision paif_conv2d_kernel_name prints. */
 int paif_conv2d_is_persistent(const paif_conv_desc* d, int B, int H, int W);
 /* The kernel paif_conv2d_fwd runs for this descriptor and shape, named as rocprofv3 lists it (without the anonymous
- * namespace and argument list), e.g. "conv_bf16x3_ms<3, 1, 2>": tile-per-workgroup (conv_mfma_bf16x3<k, d, hooks>),
- * multi-source 3x3 (conv_bf16x3_ms), resident-B persistent 3x3 (conv_bf16x3_res), wave-specialised persistent
- * (conv_bf16x3_ws), exact fp32 (conv_mfma_f32).  For timing tags and dispatch tests; writes a NUL-terminated string. */
+ * namespace and argument list; ST = the kernel's storage code), e.g. "conv_bf16x3_ms<3, 1, 2, 0>".  By family:
+ *   exact fp32                  conv_mfma_f32<k, d, cin, hooks>
+ *   three bf16 pieces           conv_mfma_bf16x6<k, d, hooks, 0>
+ *   fp16 pairs                  conv_mfma_f16x3<k, d, hooks, 0>
+ *   split bf16 / plain 16-bit   conv_mfma_bf16x3<k, d, hooks, ST> (tile per workgroup), conv_bf16x3_ms<3, 1, nsrc, ST> (multi-source 3x3),
+ *                               conv_bf16x3_res<3, 1, nsrc, rows, ST> (resident-B persistent 3x3), conv_bf16x3_ws / wsr<k, d, ST>
+ *                               (wave-specialised persistent), and on 16-bit maps with plain 16-bit weights the LDS-DMA kernels
+ *                               conv3x3_h16_dma<nsrc, nres, F, pool, d, in_act>, conv7x7_h16_dma<F>, conv_h16_dma_1x1<F>,
+ *                               conv3x3_h16_dma_rows<F, nres, out_f32> (F: 1 bf16, 2 fp16).
+ * For timing tags and dispatch tests; writes a NUL-terminated string. */
 int paif_conv2d_kernel_name(const paif_conv_desc* d, int B, int H, int W, char* buf, int buflen);
 /* w: torch layout [cout, nsrc*cin, kh, kh]; wpk: paif_conv_wpk_floats(...) floats.
  * Layout wpk[src][tap][cin/8][64 lanes][4]: lane (h = lane>>5, n = lane&31) holds

@@ -1,5 +1,5 @@
-// Interface between the dense-conv dispatcher (conv_mfma.hip) and the LDS-DMA kernels (conv_dma.hip: 3x3, 7x7; conv_dma_1x1.hip: 1x1;
-// conv_dma_rows.hip: 3x3 dilation 2 without an input activation).
+// Interface between the dense-conv dispatcher (conv_mfma.hip) and the LDS-DMA kernels: 16-bit maps (bf16 / fp16), plain 16-bit weights.
+// The dispatcher fills an Args per launch and asks classify() which form, if any, is built for it; launch() runs that form.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -24,23 +24,19 @@ struct Args {
   int out_f32;               // 1: `out` is fp32 (fp16 sources and residual maps; conv_dma_rows.hip only)
 };
 
-// true if the kernel is built for this source / residual count and the tensors fit its 32-bit addressing
-bool eligible(int nsrc, int nres, int B, int H, int W, float alpha);
-bool eligible16(int nsrc, int nres, int B, int H, int W, float alpha);  // 3x3 with 16 output channels: one source, no residual maps
-bool eligible7(int nsrc, int nres, int B, int H, int W, float alpha);   // the 7x7 form: one source, no residual maps
-bool eligible_d2(int nsrc, int nres, int B, int H, int W, float alpha);  // 3x3 dilation 2 behind an input ReLU: one source, 1 or 3 residual maps
-bool can_cpool(int nsrc, int nres, int kh, int cout, int dil);   // the instantiations that write Args::cpool
-int launch(const Args& a, hipStream_t st);
-
-// conv_dma_1x1.hip: the 1x1 over three 32-channel sources without residual maps (the folded decomposition conv) as a streaming kernel;
-// launch() hands it every Args with kh == 1.  Switch: PAIF_CONV_DMA1X1=0 (read once).
-bool eligible_1x1(int nsrc, int nres, int B, int H, int W);
-int launch_1x1(const Args& a, hipStream_t st);
-
-// conv_dma_rows.hip: the 3x3 dilation-2 conv over one 16-bit source without an input activation (0-3 residual maps, 16-bit output, or
-// fp32 from fp16 sources; no fused ChannelPool) as a row-streaming kernel.  Taken from 32,768 strip-rows (B * H * ceil(W / 32)) and
-// H >= 64.  Switch PAIF_CONV_DMA_ROWS, read per call: unset = that size rule, 0 = never, 1 = wherever the 32-bit addressing holds.
-bool eligible_rows(int nsrc, int nres, int in_relu, int cpool, int f16, int out_f32, int B, int H, int W);
-int launch_rows(const Args& a, hipStream_t st);
+// The forms.  Each kernel file holds its own part of the rule and reads its own switches:
+//   TILE        conv_dma.hip: persistent 8x32-tile kernels.  3x3 dilation 1 (1-3 sources, 0-3 residual maps, one source at most one; 16 output
+//               channels with one source and no residual map), 7x7 (one source, no residual maps), 3x3 dilation 2 behind an input ReLU (one
+//               source, 1 or 3 residual maps); alpha > 0; 1,024 to 32,768 tiles, B < 1024, 2^31 bytes per map.  Switches PAIF_CONV_DMA=0
+//               (no LDS-DMA kernel anywhere), PAIF_CONV_DMA_D2=0 (the dilation-2 form), read once.
+//   ONE_BY_ONE  conv_dma_1x1.hip: the 1x1 over three sources without residual maps (the folded decomposition conv) as a streaming kernel;
+//               2^31 bytes per map.  Switch PAIF_CONV_DMA1X1=0, read once.
+//   ROWS        conv_dma_rows.hip: the 3x3 dilation-2 conv over one source without an input activation (0-3 residual maps, 16-bit output, or
+//               fp32 from fp16 sources; no fused ChannelPool) as a row-streaming kernel.  Taken from 32,768 strip-rows (B * H * ceil(W / 32))
+//               and H >= 64.  Switch PAIF_CONV_DMA_ROWS, read per call: unset = that size rule, 0 = never, 1 = wherever the 32-bit addressing holds.
+enum Form { NONE, TILE, ONE_BY_ONE, ROWS };
+Form classify(const Args& a);
+bool can_cpool(const Args& a);             // the TILE instantiations that write Args::cpool
+int launch(const Args& a, hipStream_t st);   // the form classify() names; PAIF_ENOSUP for NONE
 
 }  // namespace paif_conv_dma

@@ -760,50 +760,65 @@ int launch_d2(const Args& a, hipStream_t st) {
 
 }  // namespace
 
-bool eligible(int nsrc, int nres, int B, int H, int W, float alpha) {
+// the forms that live in files of their own (conv_dma_1x1.hip, conv_dma_rows.hip)
+bool is_1x1(const Args& a);
+int launch_1x1(const Args& a, hipStream_t st);
+bool is_rows(const Args& a);
+int launch_rows(const Args& a, hipStream_t st);
+
+// classify()'s TILE: the kernels of this file
+static bool is_tile(const Args& a) {
   static const bool on = [] {
     const char* e = getenv("PAIF_CONV_DMA");    // PAIF_CONV_DMA=0: the register-staged kernels of conv_mfma.hip everywhere (A/B runs)
     return !(e && e[0] == '0');
   }();
-  if (!on || nsrc < 1 || nsrc > 3 || nres < 0 || nres > 3 || !(alpha > 0.f)) return false;
-  if (nsrc == 1 && nres > 1) return false;   // 4 residual register sets x 2-3 maps do not fit the register file next to the pipeline   // alpha is folded through the activation
-  const long long tiles = (long long)B * ((H + TH - 1) / TH) * ((W + TW - 1) / TW);
-  // tile table: 128 tiles per workgroup, 10 + 11 + 11 bits per entry
-  return tiles >= 1024 && tiles <= 128 * 256 && B < 1024 && H < 2048 * TH && W < 2048 * TW && (long long)B * H * W * 64 < (1ll << 31);
-}
-
-// dilation 2 with an input ReLU: one source, 1 or 3 residual maps (the register file holds the 3 residual sets of PF = 3 next to the pipeline)
-bool eligible_d2(int nsrc, int nres, int B, int H, int W, float alpha) {
-  static const bool on = [] {
+  static const bool on_d2 = [] {
     const char* e = getenv("PAIF_CONV_DMA_D2");   // PAIF_CONV_DMA_D2=0: the register-staged persistent kernel (conv_mfma.hip) for A/B runs
     return !(e && e[0] == '0');
   }();
-  return on && nsrc == 1 && (nres == 1 || nres == 3) && eligible(1, 1, B, H, W, alpha);
+  if (!on || a.out_f32 || !(a.alpha > 0.f)) return false;   // alpha is folded through the activation
+  bool built;
+  if (a.dil == 2)   // behind an input ReLU: one source, 1 or 3 residual maps (the register file holds the 3 residual sets of PF = 3 next to the pipeline)
+    built = on_d2 && a.kh == 3 && a.cout == 32 && a.in_relu && a.nsrc == 1 && (a.nres == 1 || a.nres == 3);
+  else if (a.in_relu || a.dil != 1)
+    built = false;
+  else if (a.kh == 3 && a.cout == 32)   // (one source: 4 residual register sets x 2-3 maps do not fit the register file next to the pipeline)
+    built = a.nsrc >= 1 && a.nsrc <= 3 && a.nres >= 0 && a.nres <= (a.nsrc == 1 ? 1 : 3);
+  else   // 3x3 with 16 output channels, 7x7: one source, no residual maps
+    built = ((a.kh == 3 && a.cout == 16) || (a.kh == 7 && a.cout == 32)) && a.nsrc == 1 && a.nres == 0;
+  const long long tiles = (long long)a.B * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
+  // tile table: 128 tiles per workgroup, 10 + 11 + 11 bits per entry; 32-bit addressing
+  return built && tiles >= 1024 && tiles <= 128 * 256 && a.B < 1024 && a.H < 2048 * TH && a.W < 2048 * TW &&
+         (long long)a.B * a.H * a.W * 64 < (1ll << 31);
 }
 
-bool eligible16(int nsrc, int nres, int B, int H, int W, float alpha) { return nsrc == 1 && nres == 0 && eligible(1, 0, B, H, W, alpha); }
-bool eligible7(int nsrc, int nres, int B, int H, int W, float alpha) { return nsrc == 1 && nres == 0 && eligible(1, 0, B, H, W, alpha); }
+Form classify(const Args& a) {
+  if (is_1x1(a)) return ONE_BY_ONE;
+  if (is_rows(a)) return ROWS;
+  return is_tile(a) ? TILE : NONE;
+}
 
-bool can_cpool(int nsrc, int nres, int kh, int cout, int dil) {
-  return kh == 3 && cout == 32 && ((dil == 1 && nsrc == 3 && (nres == 1 || nres == 3)) || (dil == 2 && nsrc == 1 && (nres == 1 || nres == 3)));
+bool can_cpool(const Args& a) {
+  return a.kh == 3 && a.cout == 32 && (a.nres == 1 || a.nres == 3) && ((a.dil == 1 && a.nsrc == 3) || (a.dil == 2 && a.nsrc == 1));
 }
 
 int launch(const Args& a, hipStream_t st) {
-  if (a.cpool && !can_cpool(a.nsrc, a.nres, a.kh, a.cout, a.dil)) {
+  switch (classify(a)) {
+    case ONE_BY_ONE: return launch_1x1(a, st);
+    case ROWS: return launch_rows(a, st);
+    case TILE: break;
+    default:
+      paif::set_error("conv2d(h16 dma): no LDS-DMA kernel is built for this descriptor and shape");
+      return PAIF_ENOSUP;
+  }
+  if (a.cpool && !can_cpool(a)) {
     paif::set_error("conv2d(dma): no fused ChannelPool for this form");
     return PAIF_ENOSUP;
   }
   if (a.kh == 7) return launch_7(a, st);
-  if (a.kh == 1) return launch_1x1(a, st);
   if (a.dil == 2) {
-    if (a.nsrc == 1 && a.in_relu && a.nres == 1) return a.cpool ? launch_d2<1, true>(a, st) : launch_d2<1, false>(a, st);
-    if (a.nsrc == 1 && a.in_relu && a.nres == 3) return a.cpool ? launch_d2<3, true>(a, st) : launch_d2<3, false>(a, st);
-    paif::set_error("conv2d(h16 dma): dilation 2 is built for one source behind an input ReLU with 1 or 3 residual maps");
-    return PAIF_ENOSUP;
-  }
-  if (a.in_relu) {
-    paif::set_error("conv2d(h16 dma): the input ReLU is built for the dilation-2 form");
-    return PAIF_ENOSUP;
+    if (a.nres == 1) return a.cpool ? launch_d2<1, true>(a, st) : launch_d2<1, false>(a, st);
+    return a.cpool ? launch_d2<3, true>(a, st) : launch_d2<3, false>(a, st);
   }
   switch (a.nsrc * 10 + a.nres) {
     case 10: return launch_n<1, 0>(a, st);

@@ -221,21 +221,20 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv_h16_dma_1x1(Args a, int nt
 
 }  // namespace
 
-bool eligible_1x1(int nsrc, int nres, int B, int H, int W) {
+// classify()'s ONE_BY_ONE (conv_dma.hip)
+bool is_1x1(const Args& a) {
   static const bool on = [] {
     const char* e = getenv("PAIF_CONV_DMA1X1");   // PAIF_CONV_DMA1X1=0: the persistent register-staged kernel (conv_bf16x3_ws) as before (A/B runs)
     const char* d = getenv("PAIF_CONV_DMA");      // PAIF_CONV_DMA=0: no LDS-DMA kernel anywhere
     return !(e && e[0] == '0') && !(d && d[0] == '0');
   }();
-  // 32-bit byte offsets, and the out-of-range marker above every one of them
-  return on && nsrc == 3 && nres == 0 && (long long)B * H * W * 64 < (1ll << 31);
+  // the form built: 3 sources, no residual maps, 32 output channels, 16-bit output; 32-bit byte offsets, and the out-of-range marker above
+  // every one of them
+  return on && a.kh == 1 && a.dil == 1 && a.cout == 32 && !a.in_relu && !a.out_f32 && a.nsrc == 3 && a.nres == 0 &&
+         (long long)a.B * a.H * a.W * 64 < (1ll << 31);
 }
 
 int launch_1x1(const Args& a, hipStream_t st) {
-  if (a.nsrc != 3 || a.nres != 0 || a.cout != 32 || a.cpool || a.in_relu || a.dil != 1) {
-    paif::set_error("conv2d(h16 dma 1x1): built for 3 sources, no residual maps, 32 output channels");
-    return PAIF_ENOSUP;
-  }
   const long long px = (long long)a.B * a.H * a.W;
   const int ntiles = (int)((px + TP - 1) / TP);
   if (a.f16) hipLaunchKernelGGL(conv_h16_dma_1x1<2>, dim3(GRID), dim3(WAVES * 64), 0, st, a, ntiles);

@@ -339,22 +339,20 @@ void launch_rows_f(const Args& a, hipStream_t st) {
 
 }  // namespace
 
-bool eligible_rows(int nsrc, int nres, int in_relu, int cpool, int f16, int out_f32, int B, int H, int W) {
+// classify()'s ROWS (conv_dma.hip)
+bool is_rows(const Args& a) {
+  if (a.kh != 3 || a.dil != 2 || a.cout != 32) return false;
   const int sw = env_rows();
   // the forms built: one source without an input activation, 0-3 residual maps, no fused ChannelPool; fp32 output from fp16 sources only
-  if (sw == 0 || nsrc != 1 || nres < 0 || nres > 3 || in_relu || cpool || (out_f32 && !f16)) return false;
+  if (sw == 0 || a.nsrc != 1 || a.nres < 0 || a.nres > 3 || a.in_relu || a.cpool || (a.out_f32 && !a.f16)) return false;
   // 32-bit byte offsets, and the out-of-range marker above every one of them
-  if ((long long)B * H * W * (out_f32 ? 128 : 64) >= (1ll << 31)) return false;
+  if ((long long)a.B * a.H * a.W * (a.out_f32 ? 128 : 64) >= (1ll << 31)) return false;
   if (sw == 1) return true;
   // the size rule: runs of at least MIN_RUN chain rows on every one of the 2048 waves, and chains long enough to hold them
-  return H >= 64 && (long long)B * H * ((W + RW - 1) / RW) >= (long long)MIN_RUN * MAX_WAVES;
+  return a.H >= 64 && (long long)a.B * a.H * ((a.W + RW - 1) / RW) >= (long long)MIN_RUN * MAX_WAVES;
 }
 
 int launch_rows(const Args& a, hipStream_t st) {
-  if (a.nsrc != 1 || a.cout != 32 || a.cpool || a.in_relu || a.dil != 2 || a.kh != 3 || a.nres < 0 || a.nres > 3 || (a.out_f32 && !a.f16)) {
-    paif::set_error("conv2d(h16 dma rows): built for one source, dilation 2, 0-3 residual maps, no input activation, no ChannelPool");
-    return PAIF_ENOSUP;
-  }
 #define CR_LAUNCH(NR)                                                              \
   case NR:                                                                         \
     if (a.out_f32) launch_rows_f<2, NR, true>(a, st);                              \

@@ -1300,14 +1300,6 @@ int launch_bf16x3_ms(const ConvArgs& a, hipStream_t st) {
   return 0;
 }
 
-static inline bool ms_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("PAIF_CONV_MS");   // PAIF_CONV_MS=0 keeps multi-source convs on the plain kernel (A/B runs)
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-
 
 constexpr int WS_THREADS = 12 * 64;
 
@@ -1628,213 +1620,6 @@ int launch_bf16x3_ws(const ConvArgs& a, hipStream_t st) {
   return 0;
 }
 
-// the loaders address a source image with 32-bit byte offsets; in-activations and the ECA pool stay on the plain kernel
-static inline bool ws_enabled() {
-  static const bool on = [] {
-    const char* e = getenv("PAIF_CONV_WS");   // PAIF_CONV_WS=0 selects the plain kernel everywhere (A/B runs)
-    return !(e && e[0] == '0');
-  }();
-  return on;
-}
-// 16-bit maps in AND out (bf16: 1, fp16: 3) / fp16 maps anywhere
-static inline bool st_h16(const ConvArgs& a) { return a.st == 1 || a.st == 3; }
-static inline bool st_is_f16(const ConvArgs& a) { return a.st >= 3; }
-static inline bool ws_eligible(const ConvArgs& a) {
-  return ws_enabled() && a.nblk >= 1024 && !a.pool_partial && a.cout == 32 && (a.in_act == 0 || (a.in_act == 2 && st_h16(a))) &&
-         (size_t)a.H * a.W * 128 < ((size_t)1 << 32);
-}
-
-// Resident-B persistent 3x3 (conv_bf16x3_res): one source, enough tiles to amortise the pipeline fill of 512 workgroups.
-// Measured against the tile-per-workgroup kernel at the bench shape: 165 vs 188 us.  With 2-3 sources its B refills queue
-// behind the halo prefetch of the same wave and stall the MFMA phase (400 / 544 us vs 346 / 444 us for conv_bf16x3_ms),
-// so those stay on the multi-source kernel.
-static inline bool res_eligible(const ConvArgs& a) {
-  static const bool on = [] {
-    const char* e = getenv("PAIF_CONV_RES");  // PAIF_CONV_RES=0: tile-per-workgroup kernels everywhere (A/B runs)
-    return !(e && e[0] == '0');
-  }();
-  static const int ms_res = [] {
-    const char* e = getenv("PAIF_CONV_RES_NSRC");   // experiment: largest source count the resident form takes with plain bf16 weights
-    return e ? atoi(e) : 1;
-  }();
-  return on && !st_is_f16(a) && (a.nsrc == 1 || (a.wl0 && a.st == 1 && a.in_act == 0 && a.nsrc <= ms_res)) && a.nblk >= 2048 && a.cout == 32 && a.in_act <= 2 && (PAIF_RES_ROWS == 8 || !a.pool_partial) &&
-         (size_t)a.B * a.H * a.W * 128 < ((size_t)1 << 31);   // buffer resources: 32-bit byte counts and offsets
-}
-
-static inline bool needs_hooks(const ConvArgs& a) { return a.in_act >= 3 || a.aux_out || a.epi_dact; }
-
-// Persistent wave-specialised form (needs several tiles per CU to amortise its pipeline fill).  Measured per
-// configuration against the tile-per-workgroup kernel (tools/conv_bench.py, B=8 480x640, same box,
-// profiles/r01_conv_ws_study.txt).  Since the plain kernel stages with unconditional loads (all 11 in flight) it is
-// the faster one for every 3x3 dilation-1 configuration (e.g. 1 source 191 vs 200 us, 3 sources 479 vs 567 us); the
-// persistent form keeps the pure streams: 1x1 without residual maps (119 vs 125, 171 vs 177, 232 vs 237 us -- the
-// device's copy rate) and, for bf16-stored maps, the dilation-2 3x3 with one source (222 vs 236 us).
-static inline bool takes_ws(const ConvArgs& a, int kh, int dil) {
-#if PAIF_TH == 8
-  if (needs_hooks(a) || kh > 3 || !ws_eligible(a)) return false;
-  if (a.st == 4) return dil == 2 && a.nsrc == 1 && a.in_act == 0;  // fp16 in / fp32 out: the last conv of the fp16 forward
-  if (kh == 1) return !a.res[0] && a.in_act == 0;
-  // dilation-2 3x3, one source (the composed DilConv; in_act none or ReLU): bf16-stored maps only.  With fp32 maps the tile-per-workgroup
-  // kernel is the faster one INSIDE the forward (round 4, three alternating bench.py runs each: 6.154 vs 6.173 ms per step); the 222 vs
-  // 236 us that chose the persistent form in round 1 were micro-benchmark times on random inputs, i.e. at the power-capped clock.
-  return dil == 2 && a.nsrc == 1 && st_h16(a);
-#else
-  return false;
-#endif
-}
-
-// which split-bf16 kernel a launch takes (one place: the dispatcher and paif_conv2d_kernel_name use it)
-enum ConvVariant { CV_PLAIN, CV_HOOKS, CV_WS, CV_RES, CV_MS, CV_DMA, CV_ROWS };
-static inline int res_count(const ConvArgs& a) { return a.res[0] ? (a.res[1] ? (a.res[2] ? 3 : 2) : 1) : 0; }
-static inline ConvVariant bf16x3_variant(const ConvArgs& a, int kh, int dil) {
-  if (needs_hooks(a)) return CV_HOOKS;
-  // bf16 maps + plain bf16 weights, 3x3 dilation 1, 32 -> 32 per source: the LDS-DMA kernel (conv_dma.hip)
-  if (dil == 1 && st_h16(a) && a.wl0 && a.in_act == 0 && !a.pool_partial &&
-      ((kh == 3 && a.cout == 32 && paif_conv_dma::eligible(a.nsrc, res_count(a), a.B, a.H, a.W, a.alpha)) ||
-       (kh == 3 && a.cout == 16 && paif_conv_dma::eligible16(a.nsrc, res_count(a), a.B, a.H, a.W, a.alpha)) ||
-       (kh == 7 && a.cout == 32 && paif_conv_dma::eligible7(a.nsrc, res_count(a), a.B, a.H, a.W, a.alpha))))
-    return CV_DMA;
-  // 3x3 dilation 2 without an input activation (the ResidualModule's composed conv), 16-bit source, 16-bit or fp32 output, one source,
-  // large maps: the row-streaming LDS-DMA kernel (conv_dma_rows.hip).  A launch with a fused ChannelPool stays on the persistent form.
-  if (kh == 3 && dil == 2 && (st_h16(a) || a.st == 4) && a.wl0 && a.in_act == 0 && !a.pool_partial && !a.cpool && a.cout == 32 &&
-      paif_conv_dma::eligible_rows(a.nsrc, res_count(a), 0, 0, st_is_f16(a) ? 1 : 0, a.st == 4 ? 1 : 0, a.B, a.H, a.W))
-    return CV_ROWS;
-  // round 6: 3x3 dilation 2 behind an input ReLU (the composed DilConv), 16-bit maps in and out, one source, 1 or 3 residual maps
-  if (kh == 3 && dil == 2 && st_h16(a) && a.wl0 && a.in_act == 2 && !a.pool_partial && a.cout == 32 &&
-      paif_conv_dma::eligible_d2(a.nsrc, res_count(a), a.B, a.H, a.W, a.alpha))
-    return CV_DMA;
-  // the folded decomposition 1x1 (three 16-bit sources, plain 16-bit weights, no residual maps), from the tile count at which the
-  // persistent form is taken: the streaming LDS-DMA kernel (conv_dma_1x1.hip)
-  if (kh == 1 && dil == 1 && st_h16(a) && a.wl0 && a.in_act == 0 && !a.pool_partial && a.cout == 32 && ws_eligible(a) &&
-      paif_conv_dma::eligible_1x1(a.nsrc, res_count(a), a.B, a.H, a.W))
-    return CV_DMA;
-  if (takes_ws(a, kh, dil)) return CV_WS;
-  if (kh == 3 && dil == 1 && !st_is_f16(a)) {    // (fp16 maps: LDS-DMA, persistent or tile-per-workgroup kernel only)
-    if (res_eligible(a)) return CV_RES;
-    if (ms_enabled() && a.nsrc >= 2 && a.cout == 32 && a.in_act == 0 && !a.pool_partial &&
-        (size_t)a.B * a.H * a.W * 128 < ((size_t)1 << 32))   // 32-bit byte offsets into a source
-      return CV_MS;
-  }
-  return CV_PLAIN;
-}
-
-// the fused ChannelPool (ConvArgs::cpool): every tile kernel of this file through the shared LDS epilogue / the persistent form's storers
-// (cout = 32, no gradient hooks); the LDS-DMA kernel for the source / residual counts it instantiates
-static inline bool variant_can_cpool(const ConvArgs& a, int kh, int dil) {
-  if (a.cout != 32 || needs_hooks(a)) return false;
-  if (bf16x3_variant(a, kh, dil) == CV_DMA) return paif_conv_dma::can_cpool(a.nsrc, res_count(a), kh, a.cout, dil);
-  return true;   // (CV_ROWS has no pool: the launch that carries one takes the persistent form, which has)
-}
-
-template <int KH, int DIL, int ST>
-int launch_bf16x3_st(const ConvArgs& a, hipStream_t st) {
-  const ConvVariant cv = bf16x3_variant(a, KH, DIL);
-  switch (cv) {
-    case CV_ROWS:
-    case CV_DMA: {
-      paif_conv_dma::Args d{};
-      for (int s = 0; s < 3; ++s) { d.src[s] = a.src[s]; d.res[s] = a.res[s]; }
-      d.wpk = a.wpk; d.scale = a.scale; d.shift = a.shift; d.prelu = a.prelu; d.out = a.out; d.alpha = a.alpha;
-      d.nsrc = a.nsrc; d.nres = res_count(a); d.act = a.act; d.B = a.B; d.H = a.H; d.W = a.W; d.reverse = a.reverse; d.kh = KH; d.cout = a.cout;
-      d.f16 = paif::st_f16(ST) ? 1 : 0;
-      d.cpool = a.cpool;
-      d.dil = DIL; d.in_relu = a.in_act == 2 ? 1 : 0;
-      d.out_f32 = paif::st_out(ST) == 0 ? 1 : 0;
-      return cv == CV_ROWS ? paif_conv_dma::launch_rows(d, st) : paif_conv_dma::launch(d, st);
-    }
-    case CV_HOOKS:
-      if constexpr (ST == 0) return launch_bf16x3_h<KH, DIL, true>(a, st);
-      paif::set_error("conv2d: the gradient hooks (in_act >= 3, aux_out, epi_dact) are built for fp32 storage only");
-      return PAIF_ENOSUP;
-    case CV_WS:
-#if PAIF_TH == 8
-      if constexpr (KH <= 3) return launch_bf16x3_ws<KH, DIL, ST>(a, st);
-#endif
-      break;
-    case CV_RES:
-      if constexpr (KH == 3 && DIL == 1 && !paif::st_f16(ST)) {
-        if constexpr (ST == 4) {
-          if (a.nsrc == 2) return launch_bf16x3_res<3, 1, 2, ST>(a, st);
-          if (a.nsrc == 3) return launch_bf16x3_res<3, 1, 3, ST>(a, st);
-        }
-        return launch_bf16x3_res<3, 1, 1, ST>(a, st);
-      }
-      break;
-    case CV_MS:
-      if constexpr (KH == 3 && DIL == 1 && !paif::st_f16(ST)) return a.nsrc == 2 ? launch_bf16x3_ms<3, 1, 2, ST>(a, st) : launch_bf16x3_ms<3, 1, 3, ST>(a, st);
-      break;
-    default: break;
-  }
-  return launch_bf16x3_h<KH, DIL, false, ST>(a, st);
-}
-
-// bf16 storage is built for the kernel shapes of the inference forward (1x1, 3x3 dil 1 / 2, 7x7); fp32 in / bf16 out only for
-// the 1x1 behind the fp32 guided-filter block
-// kernel storage code (template argument ST, paif_common.h) of a launch
-static inline int kernel_st(const ConvArgs& a) {
-  if (a.st == 4) return 15;                                     // fp16 in / fp32 out (plain fp16 weights)
-  const int st = a.st == 3 ? 1 : a.st;                          // fp16 in / out -> the bf16 codes' 1
-  const int base = st == 1 ? (a.in_act == 1 ? 3 : 1) : st;
-  const int code = (a.wl0 && base) ? base + 3 : base;
-  return a.st >= 3 ? code + 8 : code;
-}
-
-// three-piece split (PAIF_CONV_BF16X6): the tile-per-workgroup kernel, with or without the gradient hooks; fp32 storage
-template <int KH, int DIL>
-int launch_bf16x6(const ConvArgs& a, hipStream_t st) {
-  if (a.st != 0) {
-    paif::set_error("conv2d: precision bf16x6 is built for fp32-stored maps");
-    return PAIF_ENOSUP;
-  }
-  return needs_hooks(a) ? launch_bf16x3_h<KH, DIL, true, 0, 3>(a, st) : launch_bf16x3_h<KH, DIL, false, 0, 3>(a, st);
-}
-
-// fp16 pairs (PAIF_CONV_F16X3): the tile-per-workgroup kernel, forward form, fp32 storage
-template <int KH, int DIL>
-int launch_f16x3(const ConvArgs& a, hipStream_t st) {
-  if (a.st != 0) {
-    paif::set_error("conv2d: precision f16x3 is built for fp32-stored maps");
-    return PAIF_ENOSUP;
-  }
-  // (a saved pre-activation -- aux_out, the taped forward -- and the dgrad staging / epilogue modes take the hook kernel; a caller that
-  // sends GRADIENTS through this arithmetic scales them into fp16's exponent range first: ops.attack_grad_scale)
-  return needs_hooks(a) ? launch_bf16x3_h<KH, DIL, true, 0, 2, 1>(a, st) : launch_bf16x3_h<KH, DIL, false, 0, 2, 1>(a, st);
-}
-
-template <int KH, int DIL>
-int launch_bf16x3(const ConvArgs& a, hipStream_t st) {
-  const int code = kernel_st(a);
-  if (code == 0) return launch_bf16x3_st<KH, DIL, 0>(a, st);
-  if constexpr ((KH == 1 || KH == 3 || KH == 7) && (DIL == 1 || (KH == 3 && DIL == 2))) {
-    switch (code) {
-      case 1: return launch_bf16x3_st<KH, DIL, 1>(a, st);
-      case 3: return launch_bf16x3_st<KH, DIL, 3>(a, st);
-      case 4: return launch_bf16x3_st<KH, DIL, 4>(a, st);
-      case 6: return launch_bf16x3_st<KH, DIL, 6>(a, st);
-      default: break;
-    }
-    if constexpr (KH == 1) {
-      if (code == 2) return launch_bf16x3_st<KH, DIL, 2>(a, st);
-      if (code == 5) return launch_bf16x3_st<KH, DIL, 5>(a, st);
-    }
-    // fp16 maps (round 5): one fp16 MFMA per product (12; 14 behind an input PReLU); the folded 1x1 behind the guided filter with
-    // fp16 hi + lo weights (9); the dilation-2 3x3 that writes the forward's last map as fp32 (15)
-    switch (code) {
-      case 12: return launch_bf16x3_st<KH, DIL, 12>(a, st);
-      case 14: return launch_bf16x3_st<KH, DIL, 14>(a, st);
-      default: break;
-    }
-    if constexpr (KH == 1) {
-      if (code == 9) return launch_bf16x3_st<KH, DIL, 9>(a, st);
-    }
-    if constexpr (KH == 3 && DIL == 2) {
-      if (code == 15) return launch_bf16x3_st<KH, DIL, 15>(a, st);
-    }
-  }
-  paif::set_error("conv2d: storage %d is not built for the %dx%d dilation-%d kernel", a.st, KH, KH, DIL);
-  return PAIF_ENOSUP;
-}
-
 // w [cout][nsrc*32][kh][kh] fp32 -> wpk[src][tap][ks][hi|lo][64 lanes][8 bf16]
 __global__ void pack_weight_bf16x3_kernel(const float* __restrict__ w, unsigned short* __restrict__ wpk, int cout, int nsrc,
                                           int kh) {
@@ -1997,11 +1782,6 @@ int launch_h(const ConvArgs& a, hipStream_t st) {
   return 0;
 }
 
-template <int KH, int DIL, int CIN>
-int launch(const ConvArgs& a, hipStream_t st) {
-  return needs_hooks(a) ? launch_h<KH, DIL, CIN, true>(a, st) : launch_h<KH, DIL, CIN, false>(a, st);
-}
-
 __global__ void pack_weight_kernel(const float* __restrict__ w, float* __restrict__ wpk, int cout, int nsrc, int cin,
                                    int kh) {
   const int ntap = kh * kh, no = cin / 8;
@@ -2045,6 +1825,271 @@ __global__ void bn_fold_kernel(const float* g, const float* bta, const float* me
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Host-side dispatch.  paif_conv2d_fwd and the three queries (kernel_name, can_cpool, is_persistent) take one road:
+//   descriptor -> conv_args() -> plan_conv() -> plan_name() | plan_launch()
+// ---------------------------------------------------------------------------------------------------
+// the only place that copies descriptor fields (ConvArgs is the kernels' argument)
+ConvArgs conv_args(const paif_conv_desc* d, int B, int H, int W) {
+  ConvArgs a{};
+  for (int s = 0; s < 3; ++s) {
+    a.src[s] = s < d->nsrc ? d->src[s] : nullptr;
+    a.res[s] = d->res[s];
+  }
+  a.wpk = reinterpret_cast<const float4*>(d->wpk);
+  a.in_prelu = d->in_prelu; a.scale = d->scale; a.shift = d->shift; a.prelu = d->prelu;
+  a.out = d->out; a.pool_partial = d->pool_partial; a.cpool = d->cpool; a.alpha = d->alpha;
+  a.nsrc = d->nsrc; a.in_act = d->in_act; a.act = d->act; a.cout = d->cout;
+  a.aux_out = d->aux_out; a.in_aux = d->in_aux; a.in_scale = d->in_scale; a.in_alpha = d->in_alpha;
+  a.epi_aux = d->epi_aux; a.epi_dact = d->epi_dact;
+  a.B = B; a.H = H; a.W = W;
+  a.tilesX = (W + TW - 1) / TW; a.tilesY = (H + TH - 1) / TH; a.nblk = B * a.tilesX * a.tilesY;
+  a.reverse = d->reverse_tiles ? 1 : 0;
+  a.st = d->storage;
+  a.wl0 = (d->precision == PAIF_CONV_BF16 || d->precision == PAIF_CONV_F16) ? 1 : 0;
+  return a;
+}
+
+enum ConvFamily { FAM_F32, FAM_BF16X6, FAM_F16X3, FAM_SPLIT };   // exact fp32 | three bf16 pieces | fp16 pairs | two bf16 pieces and the 16-bit forms
+enum ConvVariant { CV_PLAIN, CV_HOOKS, CV_WS, CV_RES, CV_MS, CV_DMA, CV_ROWS };   // (FAM_SPLIT; the other families: tile per workgroup, plain or hooks)
+struct ConvPlan {
+  ConvFamily family;
+  ConvVariant variant;
+  bool hooks;              // gradient hooks (in_act >= 3, aux_out, epi_dact): the tile-per-workgroup kernel's HOOKS form
+  int st;                  // kernel storage code (template argument ST, paif_common.h); FAM_SPLIT
+  int kh, dil, cin, nres;
+  int fmt;                 // 16-bit format of the maps: 1 bf16, 2 fp16 (the LDS-DMA kernels' template argument F)
+  bool can_cpool;          // the kernel this descriptor takes WITH a pool attached writes ConvArgs::cpool
+};
+
+static inline bool env_on(const char* name) {   // a switch: NAME=0 turns its kernel off (A/B runs)
+  const char* e = getenv(name);
+  return !(e && e[0] == '0');
+}
+static inline bool needs_hooks(const ConvArgs& a) { return a.in_act >= 3 || a.aux_out || a.epi_dact; }
+static inline int res_count(const ConvArgs& a) { return a.res[0] ? (a.res[1] ? (a.res[2] ? 3 : 2) : 1) : 0; }
+
+// kernel storage code of a split-family launch
+static inline int kernel_st(const ConvArgs& a) {
+  if (a.st == 4) return 15;                                     // fp16 in / fp32 out (plain fp16 weights)
+  const int st = a.st == 3 ? 1 : a.st;                          // fp16 in / out -> the bf16 codes' 1
+  const int base = st == 1 ? (a.in_act == 1 ? 3 : 1) : st;
+  const int code = (a.wl0 && base) ? base + 3 : base;
+  return a.st >= 3 ? code + 8 : code;
+}
+
+// the LDS-DMA kernels' argument (16-bit maps, plain 16-bit weights, in_act none or ReLU: split_variant() asks for nothing else)
+static inline paif_conv_dma::Args dma_args(const ConvArgs& a, int kh, int dil) {
+  paif_conv_dma::Args d{};
+  for (int s = 0; s < 3; ++s) { d.src[s] = a.src[s]; d.res[s] = a.res[s]; }
+  d.wpk = a.wpk; d.scale = a.scale; d.shift = a.shift; d.prelu = a.prelu; d.out = a.out; d.alpha = a.alpha;
+  d.nsrc = a.nsrc; d.nres = res_count(a); d.act = a.act; d.B = a.B; d.H = a.H; d.W = a.W; d.reverse = a.reverse; d.kh = kh; d.cout = a.cout;
+  d.f16 = a.st >= 3 ? 1 : 0;
+  d.cpool = a.cpool;
+  d.dil = dil; d.in_relu = a.in_act == 2 ? 1 : 0;
+  d.out_f32 = a.st == 4 ? 1 : 0;
+  return d;
+}
+
+// Which kernel of the split family a launch takes.  The switches are read once per process.
+static ConvVariant split_variant(const ConvArgs& a, int kh, int dil) {
+  static const bool ws_on = env_on("PAIF_CONV_WS"), res_on = env_on("PAIF_CONV_RES"), ms_on = env_on("PAIF_CONV_MS");
+  static const int res_nsrc = [] {
+    const char* e = getenv("PAIF_CONV_RES_NSRC");   // experiment: largest source count the resident form takes with plain bf16 weights
+    return e ? atoi(e) : 1;
+  }();
+  if (needs_hooks(a)) return CV_HOOKS;
+  const bool h16 = a.st == 1 || a.st == 3, f16 = a.st >= 3;   // 16-bit maps in AND out (bf16 / fp16); fp16 maps anywhere
+  const size_t map_bytes = (size_t)a.B * a.H * a.W * 128;
+  // what the persistent wave-specialised form asks of a launch: several tiles per CU to amortise its pipeline fill; its loaders address a
+  // source image with 32-bit byte offsets; input PReLU and the ECA pool stay on the tile-per-workgroup kernel
+  const bool ws_fits = ws_on && a.nblk >= 1024 && !a.pool_partial && a.cout == 32 && (a.in_act == 0 || (a.in_act == 2 && h16)) &&
+                       (size_t)a.H * a.W * 128 < ((size_t)1 << 32);
+  // 16-bit maps with plain 16-bit weights: the LDS-DMA kernels, where conv_dma.h builds the form.  The streaming 1x1 is taken from the
+  // tile count at which the persistent form is; a launch with a fused ChannelPool is never ROWS (that kernel has none).
+  if ((h16 || a.st == 4) && a.wl0 && !a.pool_partial && (a.in_act == 0 || a.in_act == 2)) {
+    switch (paif_conv_dma::classify(dma_args(a, kh, dil))) {
+      case paif_conv_dma::TILE: return CV_DMA;
+      case paif_conv_dma::ROWS: return CV_ROWS;
+      case paif_conv_dma::ONE_BY_ONE:
+        if (ws_fits) return CV_DMA;
+        break;
+      default: break;
+    }
+  }
+  // Persistent wave-specialised form, measured per configuration against the tile-per-workgroup kernel (tools/conv_bench.py, B=8 480x640,
+  // profiles/r01_conv_ws_study.txt).  Since the plain kernel stages with unconditional loads (all 11 in flight) it is the faster one for
+  // every 3x3 dilation-1 configuration (e.g. 1 source 191 vs 200 us, 3 sources 479 vs 567 us); the persistent form keeps the pure
+  // streams: 1x1 without residual maps (119 vs 125, 171 vs 177, 232 vs 237 us -- the device's copy rate), the dilation-2 3x3 with one
+  // source on 16-bit maps (222 vs 236 us), and the fp16-in / fp32-out conv that ends the fp16 forward.  With fp32 maps the dilation-2 3x3 is
+  // faster tile-per-workgroup INSIDE the forward (round 4, three alternating bench.py runs each: 6.154 vs 6.173 ms per step).
+  if (PAIF_TH == 8 && kh <= 3 && ws_fits) {
+    if (a.st == 4 ? (dil == 2 && a.nsrc == 1 && a.in_act == 0) : kh == 1 ? (!a.res[0] && a.in_act == 0) : (dil == 2 && a.nsrc == 1 && h16))
+      return CV_WS;
+  }
+  if (kh == 3 && dil == 1 && !f16) {    // (fp16 maps: LDS-DMA, persistent or tile-per-workgroup kernel only)
+    // Resident-B persistent 3x3 (conv_bf16x3_res): one source, enough tiles to amortise the pipeline fill of 512 workgroups: 165 vs 188 us
+    // at the bench shape.  With 2-3 sources its B refills queue behind the halo prefetch of the same wave and stall the MFMA phase (400 /
+    // 544 us vs 346 / 444 us for conv_bf16x3_ms), so those stay on the multi-source kernel.  Buffer resources: 32-bit byte counts.
+    if (res_on && (a.nsrc == 1 || (a.wl0 && a.st == 1 && a.in_act == 0 && a.nsrc <= res_nsrc)) && a.nblk >= 2048 && a.cout == 32 &&
+        a.in_act <= 2 && (PAIF_RES_ROWS == 8 || !a.pool_partial) && map_bytes < ((size_t)1 << 31))
+      return CV_RES;
+    if (ms_on && a.nsrc >= 2 && a.cout == 32 && a.in_act == 0 && !a.pool_partial && map_bytes < ((size_t)1 << 32))   // 32-bit byte offsets into a source
+      return CV_MS;
+  }
+  return CV_PLAIN;
+}
+
+// The one decision: every entry point below asks it, and asks nothing else.
+static ConvPlan plan_conv(const ConvArgs& a, const paif_conv_desc* d) {
+  ConvPlan p{};
+  p.kh = d->kh; p.dil = d->dil; p.cin = d->cin; p.nres = res_count(a);
+  p.fmt = a.st >= 3 ? 2 : 1;
+  p.hooks = needs_hooks(a);
+  p.variant = p.hooks ? CV_HOOKS : CV_PLAIN;
+  p.family = d->precision == PAIF_CONV_BF16X6 ? FAM_BF16X6
+           : d->precision == PAIF_CONV_F16X3 ? FAM_F16X3
+           : (d->precision == PAIF_CONV_BF16X3 || d->precision == PAIF_CONV_BF16 || d->precision == PAIF_CONV_F16 || d->precision == PAIF_CONV_F16X2) ? FAM_SPLIT
+           : FAM_F32;
+  if (p.family != FAM_SPLIT || d->cin != 32) return p;
+  p.st = kernel_st(a);
+  p.variant = split_variant(a, p.kh, p.dil);
+  // The fused ChannelPool (cout = 32, no gradient hooks): every kernel of this file writes it, through the shared LDS epilogue or the
+  // persistent form's storers; the LDS-DMA tile kernels for the source / residual counts they instantiate.  Asked without a pool, the
+  // answer is about the launch WITH one: its variant can differ (CV_ROWS is not taken then).  The pointer is tested, never read through.
+  static float pool_probe;
+  ConvArgs q = a;
+  if (!q.cpool) q.cpool = &pool_probe;
+  const ConvVariant vq = a.cpool ? p.variant : split_variant(q, p.kh, p.dil);
+  p.can_cpool = a.cout == 32 && !p.hooks && (vq != CV_DMA || paif_conv_dma::can_cpool(dma_args(q, p.kh, p.dil)));
+  return p;
+}
+
+// the kernel's name as rocprofv3 prints it: every template argument, the storage code last
+static void plan_name(const ConvPlan& p, const ConvArgs& a, char* buf, int buflen) {
+  const char* hooks = p.hooks ? "true" : "false";
+  switch (p.family) {
+    case FAM_F32: snprintf(buf, buflen, "conv_mfma_f32<%d, %d, %d, %s>", p.kh, p.dil, p.cin, hooks); return;
+    case FAM_BF16X6: snprintf(buf, buflen, "conv_mfma_bf16x6<%d, %d, %s, 0>", p.kh, p.dil, hooks); return;
+    case FAM_F16X3: snprintf(buf, buflen, "conv_mfma_f16x3<%d, %d, %s, 0>", p.kh, p.dil, hooks); return;
+    case FAM_SPLIT: break;
+  }
+  switch (p.variant) {
+    case CV_DMA:
+      if (p.kh == 7) snprintf(buf, buflen, "conv7x7_h16_dma<%d>", p.fmt);
+      else if (p.kh == 1) snprintf(buf, buflen, "conv_h16_dma_1x1<%d>", p.fmt);
+      else snprintf(buf, buflen, "conv3x3_h16_dma<%d, %d, %d, %s, %d, %d>", a.nsrc, p.nres, p.fmt, a.cpool ? "true" : "false", p.dil, p.dil == 2 ? 2 : 0);
+      break;
+    case CV_ROWS: snprintf(buf, buflen, "conv3x3_h16_dma_rows<%d, %d, %s>", p.fmt, p.nres, a.st == 4 ? "true" : "false"); break;
+    case CV_WS: snprintf(buf, buflen, "conv_bf16x3_ws%s<%d, %d, %d>", a.in_act == 2 ? "r" : "", p.kh, p.dil, p.st); break;
+    case CV_RES: snprintf(buf, buflen, "conv_bf16x3_res<%d, %d, %d, %d, %d>", p.kh, p.dil, a.nsrc, PAIF_RES_ROWS, p.st); break;
+    case CV_MS: snprintf(buf, buflen, "conv_bf16x3_ms<%d, %d, %d, %d>", p.kh, p.dil, a.nsrc, p.st); break;
+    case CV_HOOKS:
+    case CV_PLAIN: snprintf(buf, buflen, "conv_mfma_bf16x3<%d, %d, %s, %d>", p.kh, p.dil, hooks, p.st); break;
+  }
+}
+
+// ... and the launch of that same name: plan_launch() picks the family, launch_key KH and DIL, launch_split the storage code, launch_split_st the variant
+static int not_built(const ConvPlan& p) {
+  static const char* const family[] = {"", "(bf16x6)", "(f16x3)", "(bf16x3)"};
+  paif::set_error("conv2d%s: kernel %dx%d dil %d cin %d not built", family[p.family], p.kh, p.kh, p.dil, p.cin);
+  return PAIF_ENOSUP;
+}
+
+template <int KH, int DIL, int ST>
+int launch_split_st(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
+  switch (p.variant) {
+    case CV_HOOKS:
+      if constexpr (ST == 0) return launch_bf16x3_h<KH, DIL, true>(a, st);
+      paif::set_error("conv2d: the gradient hooks (in_act >= 3, aux_out, epi_dact) are built for fp32 storage only");
+      return PAIF_ENOSUP;
+    case CV_WS:
+      if constexpr (PAIF_TH == 8 && KH <= 3) return launch_bf16x3_ws<KH, DIL, ST>(a, st);
+      break;
+    case CV_RES:
+      if constexpr (KH == 3 && DIL == 1 && !paif::st_f16(ST)) {
+        if constexpr (ST == 4) {
+          if (a.nsrc == 2) return launch_bf16x3_res<3, 1, 2, ST>(a, st);
+          if (a.nsrc == 3) return launch_bf16x3_res<3, 1, 3, ST>(a, st);
+        }
+        return launch_bf16x3_res<3, 1, 1, ST>(a, st);
+      }
+      break;
+    case CV_MS:
+      if constexpr (KH == 3 && DIL == 1 && !paif::st_f16(ST)) return a.nsrc == 2 ? launch_bf16x3_ms<3, 1, 2, ST>(a, st) : launch_bf16x3_ms<3, 1, 3, ST>(a, st);
+      break;
+    default: break;
+  }
+  return launch_bf16x3_h<KH, DIL, false, ST>(a, st);
+}
+
+// 16-bit storage is built for the kernel shapes of the inference forward (1x1, 3x3 dil 1 / 2, 7x7).  bf16: 1 / 3 (behind an input PReLU) and
+// 4 / 6 with plain weights; fp32 in / bf16 out (2, 5) only for the 1x1 behind the fp32 guided-filter block.  fp16: one fp16 MFMA per product
+// (12; 14 behind an input PReLU); the folded 1x1 behind the guided filter with fp16 hi + lo weights (9); the dilation-2 3x3 that writes the
+// forward's last map as fp32 (15)
+template <int KH, int DIL>
+int launch_split(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
+#define PAIF_ST_CASE(ST) case ST: return launch_split_st<KH, DIL, ST>(p, a, st);
+  if (p.st == 0) return launch_split_st<KH, DIL, 0>(p, a, st);
+  if constexpr ((KH == 1 || KH == 3 || KH == 7) && (DIL == 1 || (KH == 3 && DIL == 2))) {
+    switch (p.st) { PAIF_ST_CASE(1) PAIF_ST_CASE(3) PAIF_ST_CASE(4) PAIF_ST_CASE(6) default: break; }
+    if constexpr (KH == 1) switch (p.st) { PAIF_ST_CASE(2) PAIF_ST_CASE(5) default: break; }
+    switch (p.st) { PAIF_ST_CASE(12) PAIF_ST_CASE(14) default: break; }
+    if constexpr (KH == 1) switch (p.st) { PAIF_ST_CASE(9) default: break; }
+    if constexpr (KH == 3 && DIL == 2) switch (p.st) { PAIF_ST_CASE(15) default: break; }
+  }
+#undef PAIF_ST_CASE
+  paif::set_error("conv2d: storage %d is not built for the %dx%d dilation-%d kernel", a.st, KH, KH, DIL);
+  return PAIF_ENOSUP;
+}
+
+template <ConvFamily F, int KH, int DIL>
+int launch_k(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
+  if constexpr (F == FAM_F32) return p.hooks ? launch_h<KH, DIL, 32, true>(a, st) : launch_h<KH, DIL, 32, false>(a, st);
+  else if constexpr (F == FAM_BF16X6) return p.hooks ? launch_bf16x3_h<KH, DIL, true, 0, 3>(a, st) : launch_bf16x3_h<KH, DIL, false, 0, 3>(a, st);
+  // (fp16 pairs: a saved pre-activation -- aux_out, the taped forward -- and the dgrad staging / epilogue modes take the hook kernel; a caller
+  // that sends GRADIENTS through this arithmetic scales them into fp16's exponent range first: ops.attack_grad_scale)
+  else if constexpr (F == FAM_F16X3) return p.hooks ? launch_bf16x3_h<KH, DIL, true, 0, 2, 1>(a, st) : launch_bf16x3_h<KH, DIL, false, 0, 2, 1>(a, st);
+  else return launch_split<KH, DIL>(p, a, st);
+}
+
+// the (kh, dil, cin) built per family: one list; bf16x6 / f16x3 leave out the 5x5 / 7x7 at dilation 2, 16-channel sources are exact fp32 only
+template <ConvFamily F>
+int launch_key(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
+  constexpr bool WIDE_D2 = F == FAM_SPLIT || F == FAM_F32;
+  switch (p.kh * 100 + p.dil * 10 + (p.cin == 32 ? 0 : 1)) {
+    case 110: return launch_k<F, 1, 1>(p, a, st);
+    case 310: return launch_k<F, 3, 1>(p, a, st);
+    case 320: return launch_k<F, 3, 2>(p, a, st);
+    case 510: return launch_k<F, 5, 1>(p, a, st);
+    case 520:
+      if constexpr (WIDE_D2) return launch_k<F, 5, 2>(p, a, st);
+      break;
+    case 710: return launch_k<F, 7, 1>(p, a, st);
+    case 720:
+      if constexpr (WIDE_D2) return launch_k<F, 7, 2>(p, a, st);
+      break;
+    case 311:   // the folded decomposition conv of the exact forward
+      if constexpr (F == FAM_F32) return p.hooks ? launch_h<3, 1, 16, true>(a, st) : launch_h<3, 1, 16, false>(a, st);
+      break;
+    default: break;
+  }
+  return not_built(p);
+}
+
+// (hipcc lays the kernels out in the code object in the order this switch and the ones above name them)
+static int plan_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
+  switch (p.family) {
+    case FAM_F16X3: return launch_key<FAM_F16X3>(p, a, st);
+    case FAM_BF16X6: return launch_key<FAM_BF16X6>(p, a, st);
+    case FAM_SPLIT:
+      if (p.variant == CV_DMA || p.variant == CV_ROWS) return paif_conv_dma::launch(dma_args(a, p.kh, p.dil), st);
+      return launch_key<FAM_SPLIT>(p, a, st);
+    case FAM_F32: break;
+  }
+  return launch_key<FAM_F32>(p, a, st);
+}
+
 }  // namespace
 
 extern "C" {
@@ -2054,72 +2099,19 @@ int paif_conv2d_blocks(int B, int H, int W) { return B * ((H + TH - 1) / TH) * (
 size_t paif_conv_wpk_floats(int nsrc, int cin, int kh) { return (size_t)nsrc * kh * kh * (cin / 8) * 256; }
 
 int paif_conv2d_is_persistent(const paif_conv_desc* d, int B, int H, int W) {
-  if (!d || (d->precision != PAIF_CONV_BF16X3 && d->precision != PAIF_CONV_BF16 && d->precision != PAIF_CONV_F16 && d->precision != PAIF_CONV_F16X2) ||
-      d->cin != 32 || B <= 0 || H <= 0 || W <= 0)
-    return 0;
-  ConvArgs a{};
-  for (int s = 0; s < 3; ++s) a.res[s] = d->res[s];
-  a.pool_partial = d->pool_partial; a.nsrc = d->nsrc; a.in_act = d->in_act; a.cout = d->cout;
-  a.aux_out = d->aux_out; a.epi_dact = d->epi_dact; a.st = d->storage;
-  a.H = H; a.W = W;
-  a.nblk = B * ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-  return takes_ws(a, d->kh, d->dil) ? 1 : 0;
+  if (!d || B <= 0 || H <= 0 || W <= 0) return 0;
+  return plan_conv(conv_args(d, B, H, W), d).variant == CV_WS ? 1 : 0;
 }
 
 int paif_conv2d_can_cpool(const paif_conv_desc* d, int B, int H, int W) {
-  if (!d || d->cout != 32 || d->cin != 32 || B <= 0 || H <= 0 || W <= 0 || d->precision == PAIF_CONV_F32 || d->precision == PAIF_CONV_BF16X6 || d->precision == PAIF_CONV_F16X3) return 0;
-  ConvArgs a{};
-  for (int s = 0; s < 3; ++s) a.res[s] = d->res[s];
-  a.pool_partial = d->pool_partial; a.nsrc = d->nsrc; a.in_act = d->in_act; a.cout = d->cout;
-  a.aux_out = d->aux_out; a.epi_dact = d->epi_dact;
-  a.B = B; a.H = H; a.W = W;
-  a.nblk = B * ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-  a.st = d->storage; a.wl0 = (d->precision == PAIF_CONV_BF16 || d->precision == PAIF_CONV_F16) ? 1 : 0; a.alpha = d->alpha;
-  return variant_can_cpool(a, d->kh, d->dil) ? 1 : 0;
+  if (!d || B <= 0 || H <= 0 || W <= 0) return 0;
+  return plan_conv(conv_args(d, B, H, W), d).can_cpool ? 1 : 0;
 }
 
 int paif_conv2d_kernel_name(const paif_conv_desc* d, int B, int H, int W, char* buf, int buflen) {
   PAIF_REQUIRE(d && buf && buflen > 0 && B > 0 && H > 0 && W > 0, PAIF_EINVAL, "conv2d_kernel_name: bad arguments");
-  ConvArgs a{};
-  for (int s = 0; s < 3; ++s) a.res[s] = d->res[s];
-  a.pool_partial = d->pool_partial; a.nsrc = d->nsrc; a.in_act = d->in_act; a.cout = d->cout;
-  a.aux_out = d->aux_out; a.epi_dact = d->epi_dact;
-  a.B = B; a.H = H; a.W = W;
-  a.nblk = B * ((W + TW - 1) / TW) * ((H + TH - 1) / TH);
-  a.st = d->storage; a.wl0 = (d->precision == PAIF_CONV_BF16 || d->precision == PAIF_CONV_F16) ? 1 : 0; a.alpha = d->alpha;
-  a.cpool = d->cpool;
-  const int code = kernel_st(a);
-  if (d->precision == PAIF_CONV_BF16X6 && d->cin == 32) {
-    snprintf(buf, buflen, "conv_mfma_bf16x6<%d, %d, %s, 0>", d->kh, d->dil, needs_hooks(a) ? "true" : "false");
-    return 0;
-  }
-  if (d->precision == PAIF_CONV_F16X3 && d->cin == 32) {
-    snprintf(buf, buflen, "conv_mfma_f16x3<%d, %d, %s, 0>", d->kh, d->dil, needs_hooks(a) ? "true" : "false");
-    return 0;
-  }
-  if (d->precision != PAIF_CONV_BF16X3 && d->precision != PAIF_CONV_BF16 && d->precision != PAIF_CONV_F16 && d->precision != PAIF_CONV_F16X2) {
-    snprintf(buf, buflen, "conv_mfma_f32<%d, %d, %d, %s>", d->kh, d->dil, d->cin, needs_hooks(a) ? "true" : "false");
-    return 0;
-  }
-  if (d->cin != 32) {   // the folded decomposition conv (cin 16) runs on the exact-fp32 kernel
-    snprintf(buf, buflen, "conv_mfma_f32<%d, %d, %d, %s>", d->kh, d->dil, d->cin, needs_hooks(a) ? "true" : "false");
-    return 0;
-  }
-  // the names rocprofv3 prints: every template argument, the storage code last
-  switch (bf16x3_variant(a, d->kh, d->dil)) {
-    case CV_DMA:
-      if (d->kh == 7) snprintf(buf, buflen, "conv7x7_h16_dma<%d>", a.st >= 3 ? 2 : 1);
-      else if (d->kh == 1) snprintf(buf, buflen, "conv_h16_dma_1x1<%d>", a.st >= 3 ? 2 : 1);
-      else snprintf(buf, buflen, "conv3x3_h16_dma<%d, %d, %d, %s, %d, %d>", d->nsrc, res_count(a), a.st >= 3 ? 2 : 1, d->cpool ? "true" : "false",
-                    d->dil, d->dil == 2 ? 2 : 0);
-      break;
-    case CV_ROWS: snprintf(buf, buflen, "conv3x3_h16_dma_rows<%d, %d, %s>", a.st >= 3 ? 2 : 1, res_count(a), a.st == 4 ? "true" : "false"); break;
-    case CV_WS: snprintf(buf, buflen, "conv_bf16x3_ws%s<%d, %d, %d>", d->in_act == 2 ? "r" : "", d->kh, d->dil, code); break;
-    case CV_RES: snprintf(buf, buflen, "conv_bf16x3_res<%d, %d, %d, %d, %d>", d->kh, d->dil, d->nsrc, PAIF_RES_ROWS, code); break;
-    case CV_MS: snprintf(buf, buflen, "conv_bf16x3_ms<%d, %d, %d, %d>", d->kh, d->dil, d->nsrc, code); break;
-    case CV_HOOKS: snprintf(buf, buflen, "conv_mfma_bf16x3<%d, %d, true, %d>", d->kh, d->dil, code); break;
-    default: snprintf(buf, buflen, "conv_mfma_bf16x3<%d, %d, false, %d>", d->kh, d->dil, code); break;
-  }
+  const ConvArgs a = conv_args(d, B, H, W);
+  plan_name(plan_conv(a, d), a, buf, buflen);
   return 0;
 }
 
@@ -2131,28 +2123,12 @@ int paif_conv2d_fwd(const paif_conv_desc* d, int B, int H, int W, paif_stream_t 
   PAIF_REQUIRE(B > 0 && H > 0 && W > 0, PAIF_EINVAL, "conv2d: empty shape %dx%dx%d", B, H, W);
   PAIF_REQUIRE(d->in_act != 1 || d->in_prelu, PAIF_EINVAL, "conv2d: in_act=PReLU without slope");
   PAIF_REQUIRE(d->act != 1 || d->prelu, PAIF_EINVAL, "conv2d: act=PReLU without slope");
-  ConvArgs a;
-  for (int s = 0; s < 3; ++s) {
-    a.src[s] = s < d->nsrc ? d->src[s] : nullptr;
-    a.res[s] = d->res[s];
-  }
-  a.wpk = reinterpret_cast<const float4*>(d->wpk);
-  a.in_prelu = d->in_prelu; a.scale = d->scale; a.shift = d->shift; a.prelu = d->prelu;
-  a.out = d->out; a.pool_partial = d->pool_partial; a.cpool = d->cpool; a.alpha = d->alpha;
-  a.nsrc = d->nsrc; a.in_act = d->in_act; a.act = d->act; a.cout = d->cout;
-  a.aux_out = d->aux_out; a.in_aux = d->in_aux; a.in_scale = d->in_scale; a.in_alpha = d->in_alpha;
-  a.epi_aux = d->epi_aux; a.epi_dact = d->epi_dact;
   PAIF_REQUIRE(d->in_act >= 0 && d->in_act <= 5, PAIF_EINVAL, "conv2d: in_act=%d", d->in_act);
   PAIF_REQUIRE(!(d->in_act == 3 || d->in_act == 4) || (d->in_aux && d->nsrc == 1), PAIF_EINVAL,
                "conv2d: in_act=%d needs in_aux and a single source", d->in_act);
   PAIF_REQUIRE(d->in_act != 3 || d->in_prelu, PAIF_EINVAL, "conv2d: in_act=3 without slope");
   PAIF_REQUIRE(d->epi_dact >= 0 && d->epi_dact <= 2 && (!d->epi_dact || d->epi_aux), PAIF_EINVAL, "conv2d: epi_dact=%d", d->epi_dact);
   PAIF_REQUIRE(d->epi_dact != 1 || d->prelu, PAIF_EINVAL, "conv2d: epi_dact=PReLU without slope");
-  a.B = B; a.H = H; a.W = W;
-  a.tilesX = (W + TW - 1) / TW; a.tilesY = (H + TH - 1) / TH; a.nblk = B * a.tilesX * a.tilesY;
-  a.reverse = d->reverse_tiles ? 1 : 0;
-  a.st = d->storage;
-  a.wl0 = (d->precision == PAIF_CONV_BF16 || d->precision == PAIF_CONV_F16) ? 1 : 0;
   PAIF_REQUIRE(d->storage >= 0 && d->storage <= 4, PAIF_EINVAL, "conv2d: storage=%d", d->storage);
   const bool st_bf = d->storage == PAIF_ST_BF16 || d->storage == PAIF_ST_F32_BF16, st_hf = d->storage == PAIF_ST_F16 || d->storage == PAIF_ST_F16_F32;
   PAIF_REQUIRE(!st_bf || ((d->precision == PAIF_CONV_BF16X3 || d->precision == PAIF_CONV_BF16) && d->cin == 32), PAIF_ENOSUP,
@@ -2163,7 +2139,6 @@ int paif_conv2d_fwd(const paif_conv_desc* d, int B, int H, int W, paif_stream_t 
   PAIF_REQUIRE((d->precision != PAIF_CONV_F16 && d->precision != PAIF_CONV_F16X2) || st_hf, PAIF_ENOSUP,
                "conv2d: precision fp16 is built for fp16-stored maps only");
   PAIF_REQUIRE(d->storage != PAIF_ST_F16_F32 || d->precision == PAIF_CONV_F16, PAIF_ENOSUP, "conv2d: fp16 in / fp32 out takes plain fp16 weights");
-  hipStream_t st = paif::as_stream(stream);
   PAIF_REQUIRE(!d->cpool || paif_conv2d_can_cpool(d, B, H, W), PAIF_ENOSUP, "conv2d: no fused ChannelPool for this descriptor (paif_conv2d_can_cpool)");
   PAIF_REQUIRE(d->cin == 32 || d->cin == 16, PAIF_ENOSUP, "conv2d: cin=%d", d->cin);
   PAIF_REQUIRE(d->precision == PAIF_CONV_F32 || d->precision == PAIF_CONV_BF16X3 || d->precision == PAIF_CONV_BF16 ||
@@ -2171,58 +2146,8 @@ int paif_conv2d_fwd(const paif_conv_desc* d, int B, int H, int W, paif_stream_t 
                    d->precision == PAIF_CONV_F16X3, PAIF_EINVAL,
                "conv2d: precision=%d", d->precision);
   PAIF_REQUIRE((d->precision != PAIF_CONV_BF16X6 && d->precision != PAIF_CONV_F16X3) || d->cin == 32, PAIF_ENOSUP, "conv2d: bf16x6 / f16x3 need 32-channel sources");
-  const int key = d->kh * 100 + d->dil * 10 + (d->cin == 32 ? 0 : 1);
-  if (d->precision == PAIF_CONV_F16X3) {
-    switch (key) {
-      case 110: return launch_f16x3<1, 1>(a, st);
-      case 310: return launch_f16x3<3, 1>(a, st);
-      case 320: return launch_f16x3<3, 2>(a, st);
-      case 510: return launch_f16x3<5, 1>(a, st);
-      case 710: return launch_f16x3<7, 1>(a, st);
-      default: break;
-    }
-    paif::set_error("conv2d(f16x3): kernel %dx%d dil %d cin %d not built", d->kh, d->kh, d->dil, d->cin);
-    return PAIF_ENOSUP;
-  }
-  if (d->precision == PAIF_CONV_BF16X6) {
-    switch (key) {
-      case 110: return launch_bf16x6<1, 1>(a, st);
-      case 310: return launch_bf16x6<3, 1>(a, st);
-      case 320: return launch_bf16x6<3, 2>(a, st);
-      case 510: return launch_bf16x6<5, 1>(a, st);
-      case 710: return launch_bf16x6<7, 1>(a, st);
-      default: break;
-    }
-    paif::set_error("conv2d(bf16x6): kernel %dx%d dil %d cin %d not built", d->kh, d->kh, d->dil, d->cin);
-    return PAIF_ENOSUP;
-  }
-  if (d->precision == PAIF_CONV_BF16X3 || d->precision == PAIF_CONV_BF16 || d->precision == PAIF_CONV_F16 || d->precision == PAIF_CONV_F16X2) {
-    switch (key) {
-      case 110: return launch_bf16x3<1, 1>(a, st);
-      case 310: return launch_bf16x3<3, 1>(a, st);
-      case 320: return launch_bf16x3<3, 2>(a, st);
-      case 510: return launch_bf16x3<5, 1>(a, st);
-      case 520: return launch_bf16x3<5, 2>(a, st);
-      case 710: return launch_bf16x3<7, 1>(a, st);
-      case 720: return launch_bf16x3<7, 2>(a, st);
-      default: break;
-    }
-    paif::set_error("conv2d(bf16x3): kernel %dx%d dil %d cin %d not built", d->kh, d->kh, d->dil, d->cin);
-    return PAIF_ENOSUP;
-  }
-  switch (key) {
-    case 110: return launch<1, 1, 32>(a, st);
-    case 310: return launch<3, 1, 32>(a, st);
-    case 320: return launch<3, 2, 32>(a, st);
-    case 510: return launch<5, 1, 32>(a, st);
-    case 520: return launch<5, 2, 32>(a, st);
-    case 710: return launch<7, 1, 32>(a, st);
-    case 720: return launch<7, 2, 32>(a, st);
-    case 311: return launch<3, 1, 16>(a, st);
-    default: break;
-  }
-  paif::set_error("conv2d: kernel %dx%d dil %d cin %d not built", d->kh, d->kh, d->dil, d->cin);
-  return PAIF_ENOSUP;
+  const ConvArgs a = conv_args(d, B, H, W);
+  return plan_launch(plan_conv(a, d), a, paif::as_stream(stream));
 }
 
 int paif_pack_conv_weight_bf16x3(const float* w, float* wpk, int cout, int nsrc, int kh, paif_stream_t stream) {

@@ -278,7 +278,7 @@ def _epilogue(z, case, scale, shift, slope, res):
 
 
 def _desc(case, res16, comp):
-    """The fields the dispatcher reads (bf16x3_variant / kernel_st in csrc/conv_mfma.hip): storage, precision, nsrc, cin, kh, dil,
+    """The fields the dispatcher reads (plan_conv in csrc/conv_mfma.hip): storage, precision, nsrc, cin, kh, dil,
     cout, alpha, in_act, which res pointers are set, cpool (and pool_partial / the gradient hooks, unset here as in ops.conv2d
     for these calls).  storage and precision restate what ops.conv2d derives from the dtypes and the weight pack."""
     d = _lib.ConvDesc()
