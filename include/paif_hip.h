@@ -788,6 +788,32 @@ int paif_reconet_step_bwd(const float* i1, size_t sb1, const float* i2, size_t s
                           const float* att_b, const float* f_next, const float* d_f_next, const float* pack, int dim, float* d_i1,
                           float* d_i2, float* d_f_prev, float* workspace, int accumulate, int B, int H, int W, paif_stream_t stream);
 
+/* SDNet baseline (fusion_model/SDNet.py of the reference; csrc/sdnet.hip).  fp32 throughout.  feat / dfeat: the eight 16-channel maps
+ * and their gradients, NHWC, ONE allocation each of 2 * 4 * B*H*W*16 floats indexed [encoder 0/1][level 0..3][B][H][W][16] (level l of
+ * encoder e is conv(l+1)(e+1): x11 .. x14, x21 .. x24).  Every launch covers both encoders.  x1 / x2 are addressed as plane b at
+ * x1 + b * sb1 (floats); every other plane is dense [B,H,W].  pack: paif_sdnet_pack_floats() floats, written by nine
+ * paif_sdnet_pack_conv calls.  No host synchronisation, no allocation: capturable.  Bit-reproducible (no atomics). */
+size_t paif_sdnet_pack_floats(void);
+/* fusion_model/SDNet.py:9-21: one Conv2d's weight and bias into the kernels' operand order.  layer 0: conv11 / conv12 ([16,1,5,5]),
+ * 1..3: conv21 / conv22, conv31 / conv32, conv41 / conv42 ([16,16*layer,3,3]), 4: fuse ([1,128,1,1], encoder ignored). */
+int paif_sdnet_pack_conv(const float* w, const float* b, int layer, int encoder, float* pack, paif_stream_t stream);
+/* fusion_model/SDNet.py:34, :39: level 0 = LeakyReLU(conv 5x5, pad 2, 1 -> 16) of both planes. */
+int paif_sdnet_stem_fwd(const float* x1, size_t sb1, const float* x2, size_t sb2, const float* pack, float* feat, int B, int H, int W,
+                        paif_stream_t stream);
+/* fusion_model/SDNet.py:35-37, :40-42: level (1..3) = LeakyReLU(conv 3x3, pad 1, over the concat of levels 0 .. level-1), an implicit
+ * GEMM on v_mfma_f32_16x16x4_f32; reads the lower levels of feat, writes level `level`. */
+int paif_sdnet_dense_fwd(const float* pack, float* feat, int level, int B, int H, int W, paif_stream_t stream);
+/* fusion_model/SDNet.py:44: out = tanh(conv 1x1, 128 -> 1, over the concat of the eight maps). */
+int paif_sdnet_fuse_fwd(const float* pack, const float* feat, float* out, int B, int H, int W, paif_stream_t stream);
+/* Reverse of fusion_model/SDNet.py:44: dy = d_out * (1 - out^2); WRITES all eight maps of dfeat (nothing needs a memset). */
+int paif_sdnet_fuse_bwd(const float* pack, const float* out, const float* d_out, float* dfeat, int B, int H, int W, paif_stream_t stream);
+/* Reverse of fusion_model/SDNet.py:35-37, :40-42 (input gradients): through the LeakyReLU of level `level` (branch from the taped
+ * output, out > 0) and the transposed 3x3 conv, ADDED to the levels below it in dfeat.  Call with level 3, 2, 1 in that order. */
+int paif_sdnet_dense_bwd(const float* pack, const float* feat, float* dfeat, int level, int B, int H, int W, paif_stream_t stream);
+/* Reverse of fusion_model/SDNet.py:34, :39: level 0 of dfeat through the LeakyReLU and the transposed 5x5 conv -> d_x1, d_x2 (written). */
+int paif_sdnet_stem_bwd(const float* pack, const float* feat, const float* dfeat, float* d_x1, float* d_x2, int B, int H, int W,
+                        paif_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

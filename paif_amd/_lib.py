@@ -206,6 +206,14 @@ SIGNATURES = {
     "paif_reconet_init_bwd": (c_int, [F, c_size_t, F, c_size_t, c_int, F, F, F, c_int, c_int, c_int, F]),
     "paif_reconet_step_fwd": (c_int, [F, c_size_t, F, c_size_t, F, F, c_int, F, F, F, c_int, c_int, c_int, F]),
     "paif_reconet_step_bwd": (c_int, [F, c_size_t, F, c_size_t, F, F, F, F, F, F, c_int, F, F, F, F, c_int, c_int, c_int, c_int, F]),
+    "paif_sdnet_pack_floats": (c_size_t, []),
+    "paif_sdnet_pack_conv": (c_int, [F, F, c_int, c_int, F, F]),
+    "paif_sdnet_stem_fwd": (c_int, [F, c_size_t, F, c_size_t, F, F, c_int, c_int, c_int, F]),
+    "paif_sdnet_dense_fwd": (c_int, [F, F, c_int, c_int, c_int, c_int, F]),
+    "paif_sdnet_fuse_fwd": (c_int, [F, F, F, c_int, c_int, c_int, F]),
+    "paif_sdnet_fuse_bwd": (c_int, [F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_sdnet_dense_bwd": (c_int, [F, F, F, c_int, c_int, c_int, c_int, F]),
+    "paif_sdnet_stem_bwd": (c_int, [F, F, F, F, F, c_int, c_int, c_int, F]),
 }
 
 _lib = None

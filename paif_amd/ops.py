@@ -2208,3 +2208,46 @@ def reconet_step_bwd(i1, i2, f_prev, att_a, att_b, f_next, d_f_next, pack, dim, 
     _lib.check(lib().paif_reconet_step_bwd(p1, s1, p2, s2, _p(f_prev), _p(att_a), _p(att_b), _p(f_next), _p(d_f_next), _p(pack), dim, _p(d_i1), _p(d_i2),
                                            _p(d_f_prev), _p(workspace), int(accumulate), B, H, W, _stream()), "reconet_step_bwd")
     return d_f_prev
+
+
+# ---------------------------------------------------------------------------------------------
+# SDNet baseline (csrc/sdnet.hip; fusion_model/sdnet.py is the module)
+# ---------------------------------------------------------------------------------------------
+def sdnet_pack(convs):
+    """convs: nine (layer, encoder, weight, bias) -- layer 0 the 5x5 stems, 1..3 the dense 3x3 convs, 4 the fuse 1x1 -> the kernels'
+    weight layout (the dense convs in MFMA operand order, forward and reverse)."""
+    dev = convs[0][2].device
+    pack = torch.zeros(lib().paif_sdnet_pack_floats(), device=dev, dtype=torch.float32)
+    for layer, enc, w, b in convs:
+        _lib.check(lib().paif_sdnet_pack_conv(_p(w.detach().contiguous()), _p(b.detach().contiguous()), layer, enc, _p(pack), _stream()),
+                   "sdnet_pack_conv")
+    return pack
+
+
+def sdnet_forward(x1, x2, pack):
+    """Two [B,1,H,W] planes -> (feat [2,4,B,H,W,16]: the eight LeakyReLU maps, NHWC; fused [B,1,H,W]).  Five launches."""
+    B, _, H, W = x1.shape
+    x1, p1, s1 = _plane(x1)
+    x2, p2, s2 = _plane(x2)
+    L = lib()
+    feat = torch.empty((2, 4, B, H, W, 16), device=x1.device, dtype=torch.float32)
+    out = torch.empty((B, 1, H, W), device=x1.device, dtype=torch.float32)
+    _lib.check(L.paif_sdnet_stem_fwd(p1, s1, p2, s2, _p(pack), _p(feat), B, H, W, _stream()), "sdnet_stem_fwd")
+    for level in (1, 2, 3):
+        _lib.check(L.paif_sdnet_dense_fwd(_p(pack), _p(feat), level, B, H, W, _stream()), "sdnet_dense_fwd")
+    _lib.check(L.paif_sdnet_fuse_fwd(_p(pack), _p(feat), _p(out), B, H, W, _stream()), "sdnet_fuse_fwd")
+    return feat, out
+
+
+def sdnet_backward(feat, out, d_out, pack):
+    """Reverse of sdnet_forward (input gradients) from the taped maps and fused plane -> (d_x1, d_x2) [B,1,H,W].  Five launches."""
+    B, _, H, W = out.shape
+    L = lib()
+    d_out = d_out.contiguous()
+    dfeat = torch.empty_like(feat)
+    d1, d2 = torch.empty_like(out), torch.empty_like(out)
+    _lib.check(L.paif_sdnet_fuse_bwd(_p(pack), _p(out), _p(d_out), _p(dfeat), B, H, W, _stream()), "sdnet_fuse_bwd")
+    for level in (3, 2, 1):
+        _lib.check(L.paif_sdnet_dense_bwd(_p(pack), _p(feat), _p(dfeat), level, B, H, W, _stream()), "sdnet_dense_bwd")
+    _lib.check(L.paif_sdnet_stem_bwd(_p(pack), _p(feat), _p(dfeat), _p(d1), _p(d2), B, H, W, _stream()), "sdnet_stem_bwd")
+    return d1, d2
