@@ -222,6 +222,19 @@ int paif_spa_blend_fwd_f16(const float* comp, const float* w, const float* ir, c
 int paif_eca_finish_fwd_f16(const float* o, const float* r, const float* pool_partial, const float* w1d, int k,
                             const float* prelu, float* gate, float* out, int B, int H, int W, paif_stream_t stream);
 int paif_tail_fwd_f16(const float* x, const float* w, const float* prelu, float* fused, int B, int H, int W, paif_stream_t stream);
+/* The tail of ECABasicBlock (operations_m.py:368-393) on fp16 maps in three launches that never store conv2's output map
+ * (csrc/conv_eca_rows.hip): conv2 over PReLU(r, in_prelu) for the per-tile pool partials (pool_partial: paif_conv2d_blocks(B, H, W) * 32
+ * floats), the gate (gate: B * 32 floats), conv2 again with out = fp16(PReLU(fp16(o) * gate + r, prelu)).  r, out: fp16 NHWC-32 behind
+ * the float*; wpk: the fp16 pack of conv2's 32 -> 32 3x3 weight (paif_pack_conv_weight, PAIF_CONV_F16).  Bit-identical to
+ * paif_conv2d_fwd (in_act = PReLU, pool_partial) + paif_eca_finish_fwd_f16.  Allocates nothing; capture-safe.  Returns PAIF_ENOSUP where
+ * B * H * W * 64 bytes reach 2^31 -- every smaller shape, ragged H and W included, is supported.
+ * paif_eca_conv2_gated_fits: 1 where callers should take this entry.  Environment PAIF_ECA_ROWS, read per call: unset = from 32,768
+ * strip-rows (B * H * ceil(W / 32)) and H >= 64, 0 = never, 1 = every supported shape.
+ * paif_eca_conv2_staged_f16 is a test hook: out = the operand rows exactly as the kernels stage them, fp16(PReLU(r, in_prelu)). */
+int paif_eca_conv2_gated_fits(int B, int H, int W);
+int paif_eca_conv2_gated_fwd_f16(const float* r, const float* wpk, const float* in_prelu, float* pool_partial, const float* w1d, int k,
+                                 const float* prelu, float* gate, float* out, int B, int H, int W, paif_stream_t stream);
+int paif_eca_conv2_staged_f16(const float* r, const float* wpk, const float* in_prelu, float* out, int B, int H, int W, paif_stream_t stream);
 int paif_add_fwd_f16(const float* a, const float* b, float* out, size_t n, paif_stream_t stream);
 
 int paif_conv2d_blocks(int B, int H, int W);

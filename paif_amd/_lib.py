@@ -144,6 +144,9 @@ SIGNATURES = {
     "paif_spa_blend_fwd_f16": (c_int, [F, F, F, F, F, c_int, c_int, c_int, F]),
     "paif_eca_finish_fwd_f16": (c_int, [F, F, F, F, c_int, F, F, F, c_int, c_int, c_int, F]),
     "paif_tail_fwd_f16": (c_int, [F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_eca_conv2_gated_fits": (c_int, [c_int, c_int, c_int]),
+    "paif_eca_conv2_gated_fwd_f16": (c_int, [F, F, F, F, F, c_int, F, F, F, c_int, c_int, c_int, F]),
+    "paif_eca_conv2_staged_f16": (c_int, [F, F, F, F, c_int, c_int, c_int, F]),
     "paif_add_fwd_f16": (c_int, [F, F, F, c_size_t, F]),
     "paif_cast_storage_fwd": (c_int, [F, F, c_size_t, c_int, F]),
     "paif_attack_loss_blocks": (c_int, [c_int, c_int, c_int]),

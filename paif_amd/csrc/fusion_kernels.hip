@@ -5,6 +5,7 @@
 // deterministic (per-block partials reduced in a fixed order, no float atomics).
 #include <stdarg.h>
 
+#include "conv_eca_rows.h"
 #include "paif_common.h"
 
 namespace paif {
@@ -997,6 +998,38 @@ int paif_eca_finish_fwd_bf16(const float* o, const float* r, const float* pool_p
 int paif_eca_finish_fwd_f16(const float* o, const float* r, const float* pool_partial, const float* w1d, int k, const float* prelu,
                             float* gate, float* out, int B, int H, int W, paif_stream_t stream) {
   return eca_finish16<2>(o, r, pool_partial, w1d, k, prelu, gate, out, B, H, W, stream);
+}
+
+/* ECABasicBlock's tail on fp16 maps without the map o (csrc/conv_eca_rows.hip): conv2 for the pool partials, the gate, conv2 again with the
+ * gated epilogue.  mode as PAIF_ECA_ROWS reads it: -1 the size rule, 1 wherever the 32-bit addressing holds. */
+int paif_eca_conv2_gated_fits(int B, int H, int W) {
+  const int sw = paif_eca_rows::env_switch();
+  if (sw == 0) return 0;
+  return (sw == 1 ? paif_eca_rows::fits(B, H, W) : paif_eca_rows::by_size_rule(B, H, W)) ? 1 : 0;
+}
+int paif_eca_conv2_gated_fwd_f16(const float* r, const float* wpk, const float* in_prelu, float* pool_partial, const float* w1d, int k,
+                                 const float* prelu, float* gate, float* out, int B, int H, int W, paif_stream_t stream) {
+  PAIF_REQUIRE(r && wpk && in_prelu && pool_partial && w1d && prelu && gate && out && B > 0 && H > 0 && W > 0, PAIF_EINVAL,
+               "eca_conv2_gated: bad arguments");
+  PAIF_REQUIRE(k >= 1 && k <= 9 && (k & 1), PAIF_ENOSUP, "eca_conv2_gated: k=%d", k);
+  PAIF_REQUIRE(paif_eca_rows::fits(B, H, W), PAIF_ENOSUP, "eca_conv2_gated: %d x %d x %d x 32 fp16 does not fit 32-bit byte offsets", B, H, W);
+  hipStream_t st = paif::as_stream(stream);
+  paif_eca_rows::Args a = {};
+  a.r = r; a.wpk = wpk; a.in_prelu = in_prelu; a.prelu = prelu; a.gate = gate; a.partial = pool_partial; a.out = out;
+  a.B = B; a.H = H; a.W = W;
+  int e = paif_eca_rows::launch(paif_eca_rows::POOL, a, st);
+  if (e) return e;
+  hipLaunchKernelGGL(eca_scale_kernel, dim3(B), dim3(1024), 0, st, pool_partial, w1d, k, paif_conv2d_blocks(1, H, W), 1.0f / ((float)H * (float)W), gate);
+  PAIF_LAUNCH_CHECK("eca_scale");
+  return paif_eca_rows::launch(paif_eca_rows::GATED, a, st);
+}
+/* Test hook: the operand rows of that conv2 as its kernels stage them, out = fp16(PReLU(r)) through the ring's in-place rewrite. */
+int paif_eca_conv2_staged_f16(const float* r, const float* wpk, const float* in_prelu, float* out, int B, int H, int W, paif_stream_t stream) {
+  PAIF_REQUIRE(r && wpk && in_prelu && out && paif_eca_rows::fits(B, H, W), PAIF_EINVAL, "eca_conv2_staged: bad arguments");
+  paif_eca_rows::Args a = {};
+  a.r = r; a.wpk = wpk; a.in_prelu = in_prelu; a.out = out;
+  a.B = B; a.H = H; a.W = W;
+  return paif_eca_rows::launch(paif_eca_rows::STAGED, a, paif::as_stream(stream));
 }
 int paif_tail_fwd_bf16(const float* x, const float* w, const float* prelu, float* fused, int B, int H, int W, paif_stream_t stream) {
   return tail16<1>(x, w, prelu, fused, B, H, W, stream);

@@ -554,12 +554,11 @@ class ECABasicBlock(_HipOp):
         a = self.relu.weight
         w1 = self._packs.get("w1", [self.conv1.weight], lambda: ops.pack_conv_weight(self.conv1.weight, 1, 32, 3))
         r = ops.conv2d([x], w1, 3, 1)
+        if tape is None:     # (large fp16 maps: conv2 twice on a row-streaming kernel, o never stored; else the two calls below)
+            return self._add_res(ops.eca_block_tail(r, self.conv2.wpk(1, 32), self.k, self.se.conv.weight, a), res)
         o, partial = ops.conv2d([r], self.conv2.wpk(1, 32), self.k, 1, in_act=ops.ACT_PRELU, in_prelu=a, pool=True)
-        if tape is None:
-            out = ops.eca_finish(o, r, partial, self.se.conv.weight, self.k, a)
-        else:
-            out, u, gate = ops.eca_finish(o, r, partial, self.se.conv.weight, self.k, a, save=True)
-            tape.append(dict(r=r, o=o, u=u, gate=gate, x=x, pool=partial) if ops.taping_wgrad() else dict(r=r, o=o, u=u, gate=gate))
+        out, u, gate = ops.eca_finish(o, r, partial, self.se.conv.weight, self.k, a, save=True)
+        tape.append(dict(r=r, o=o, u=u, gate=gate, x=x, pool=partial) if ops.taping_wgrad() else dict(r=r, o=o, u=u, gate=gate))
         return self._add_res(out, res)
 
     bwd_takes_res = True    # see ResidualDenseBlock

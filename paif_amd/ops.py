@@ -1045,6 +1045,30 @@ def eca_finish(o, r, partial, w1d, k, prelu, save=False):
     return (out, u, gate) if save else out
 
 
+ECA_ROWS_TAG = "eca_conv2_rows<0> + eca_scale_kernel + eca_conv2_rows<1>"     # the three launches of paif_eca_conv2_gated_fwd_f16
+
+
+def eca_block_tail(r, wpk, k, w1d, prelu):
+    """ECABasicBlock behind its conv1 (inference): PReLU(o * gate + r), o = conv_k(PReLU(r)), gate = sigmoid(conv1d(mean o)).
+    fp16 maps with plain fp16 weights at the sizes paif_eca_conv2_gated_fits names (PAIF_ECA_ROWS): conv2 runs twice as a row-streaming
+    kernel and o is never stored (csrc/conv_eca_rows.hip); everything else: conv2d(pool=True) + eca_finish.  Bit-identical either way."""
+    B, H, W, C = r.shape
+    L = lib()
+    if r.dtype == torch.float16 and C == 32 and k == 3 and wpk.precision == "f16" and L.paif_eca_conv2_gated_fits(B, H, W):
+        out = torch.empty_like(r)
+        partial = torch.empty((L.paif_conv2d_blocks(B, H, W), 32), device=r.device, dtype=torch.float32)
+        gate = torch.empty((B, 32), device=r.device, dtype=torch.float32)
+        e0 = TIMER.start(ECA_ROWS_TAG) if TIMER is not None else None
+        _lib.check(L.paif_eca_conv2_gated_fwd_f16(_pa(r), _p(wpk.data), _p(prelu), _p(partial), _p(w1d.detach().contiguous()), k, _p(prelu),
+                                                  _p(gate), _pa(out), B, H, W, _stream()), "eca_conv2_gated")
+        if e0 is not None:      # conv2 twice; r read twice, out written once (the partials and the gate are noise)
+            px = B * H * W
+            TIMER.stop(ECA_ROWS_TAG, e0, 2 * 2 * px * 9 * 32 * 32, px * 2 * 32 * 3)
+        return out
+    o, partial = conv2d([r], wpk, k, 1, in_act=ACT_PRELU, in_prelu=prelu, pool=True)
+    return eca_finish(o, r, partial, w1d, k, prelu)
+
+
 def eca_layer_fwd(x, w1d, k):
     """Stand-alone eca_layer.forward (operations_m.py:353-367) on an NHWC fp32 map: x * sigmoid(conv1d_k(avgpool(x))) -- the pooling
     kernel + the fused block's own finish kernel (zero residual, PReLU slope 1 = identity)."""

@@ -1,5 +1,6 @@
 """Static check of a hipcc -S listing: between an inline-asm ds_read_b128 and the next s_waitcnt lgkmcnt, no instruction may touch the
-read's destination registers (hipcc does not know the load is in flight and will happily copy them).  usage: check_asm_lds_hazard.py file.s"""
+read's destination registers (hipcc does not know the load is in flight and will happily copy them).  LDS stores and ds_bpermute take a
+place in the same in-order queue lgkmcnt counts (conv_eca_rows.hip rewrites a row piece between two batches of reads).  usage: check_asm_lds_hazard.py file.s"""
 import re, sys
 L = open(sys.argv[1]).read().split('\n')
 bad = 0
@@ -30,4 +31,6 @@ for i, ln in enumerate(L):
             for (lo, hi) in pend:
                 if a <= hi and b >= lo:
                     print("HAZARD", fn[50:72] if fn else '?', 'line', i + 1, s, 'pending', (lo, hi)); bad += 1
+    if s.startswith('ds_write') or s.startswith('ds_bpermute'):
+        pend.append((-1, -1))       # counted by lgkmcnt, no destination to protect
 print("hazards:", bad)
