@@ -26,13 +26,12 @@
 #include <type_traits>
 
 #include "conv_dma.h"
-#include "paif_common.h"
+#include "conv_rows.h"
 
 namespace paif_conv_dma {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace paif_rows;   // the primitives only: this file's tile kernels are a schedule of their own
 constexpr int TW = 32, TH = 8;          // output tile
 #ifndef CD_PF
 #define CD_PF 4
@@ -63,18 +62,10 @@ struct Geo {
   // fragments feed six MFMAs at either dilation (rows 2 w, 2 w + 1 would need six fragments at dilation 2)
   static __device__ __forceinline__ int base_row(int w) { return DIL == 1 ? 2 * w : (w >> 1) * 4 + (w & 1); }
 };
-constexpr unsigned RSRC_W3 = 0x00020000u;
-constexpr unsigned OOB = 0x80000000u;   // a byte offset no map reaches (checked at launch): the hardware returns 0 / drops the store
 constexpr int NSTORE = 4;               // 16-byte stores per wave and tile (2 rows x 32 px x 64 B)
 constexpr int VMCAP = 63;
 
-#define CD_VMWAIT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"((n) > VMCAP ? VMCAP : (n)) : "memory")
-#define CD_RD128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#define CD_WR32(addr, val, off) asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(addr), "v"(val), "n"(off) : "memory")
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned lds_off) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)lds_off, 16, voff, 0, 0, 0);
-}
+#define CD_VMWAIT(n) ROWS_VMWAIT((n) > VMCAP ? VMCAP : (n))   // a count past the 6 bits of vmcnt waits for more than it must
 
 // The vector-memory pattern of a stage (tile t, source s), in issue order:
 //   (a) s == R_STAGE: 4 x NRES residual loads of tile t + D     (b) 6 DMAs of stage g + PF     (c) s == 0: 4 stores of tile t - 1
@@ -308,12 +299,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
       if constexpr (S == 0) {                              // read the previous tile back from its transposition buffer, [pixel][channel]
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
-          CD_RD128(t[it][0], a_pr, it * 2048);
-          CD_RD128(t[it][1], a_pr, it * 2048 + 16);
+          ROWS_RD128(t[it][0], a_pr, it * 2048);
+          ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
         }
       }
 #pragma unroll
-      for (int r = 0; r < 4; ++r) CD_RD128(A[0][r], ad[0][0], r * DIL * ROWB);
+      for (int r = 0; r < 4; ++r) ROWS_RD128(A[0][r], ad[0][0], r * DIL * ROWB);
     }
     // (a) residual maps, D tiles ahead
     if constexpr (NRES > 0 && S == SC::R_STAGE) issue_res(std::integral_constant<int, (K + D) % U>{}, k + D);
@@ -321,7 +312,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
     // (b) the DMAs of stage g + PF
     if constexpr ((S + PF) % NSRC == 0) target(k + (S + PF) / NSRC);
 #pragma unroll
-    for (int i = 0; i < DPW; ++i) dma16(rs_src[(S + PF) % NSRC], d_voff[i], (unsigned)(fill * SLOT + (w * DPW + i) * 1024));
+    for (int i = 0; i < DPW; ++i) dma16<0>(rs_src[(S + PF) % NSRC], d_voff[i], (unsigned)(fill * SLOT + (w * DPW + i) * 1024));
     if constexpr (VIRT) {
       if constexpr (S == 0) {   // (c)
 #pragma unroll
@@ -359,7 +350,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
         if constexpr (gi + 1 < 6) {
           constexpr int ks1 = (gi + 1) / 3, dx1 = (gi + 1) % 3;
 #pragma unroll
-          for (int r = 0; r < 4; ++r) CD_RD128(A[(gi + 1) & 1][r], ad[dx1][ks1], r * DIL * ROWB);
+          for (int r = 0; r < 4; ++r) ROWS_RD128(A[(gi + 1) & 1][r], ad[dx1][ks1], r * DIL * ROWB);
         }
         if constexpr (S == 0 && gi == 0) {   // LDS operations complete in order: the read-back issued in front of A[0] is in `t` too
           asm volatile("s_waitcnt lgkmcnt(4)"
@@ -394,7 +385,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
             const float v = acc[j][r];
-            CD_WR32(a_pw, v, (j * 32 + (r & 3) + 8 * (r >> 2)) * 128);
+            ROWS_WR32(a_pw, v, (j * 32 + (r & 3) + 8 * (r >> 2)) * 128);
           }
       }
     }
@@ -405,8 +396,8 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
     constexpr int K = decltype(ktag)::value;
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
-      CD_RD128(t[it][0], a_pr, it * 2048);
-      CD_RD128(t[it][1], a_pr, it * 2048 + 16);
+      ROWS_RD128(t[it][0], a_pr, it * 2048);
+      ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
     }
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1]), "+v"(t[2][0]), "+v"(t[2][1]), "+v"(t[3][0]), "+v"(t[3][1])::"memory");
@@ -482,8 +473,6 @@ static_assert(LDS_BYTES <= 160 * 1024, "7x7: ring + weights + transposition buff
 static_assert(4 * DPW * 64 >= NPIX * 4, "7x7: DMA instructions do not cover the halo tile");
 }  // namespace k7
 
-#define CD_WR128(addr, val, off) asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(val), "n"(off) : "memory")
-
 template <int F>
 __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, int tilesX, int tilesY) {
   constexpr int P = k7::P, TWH = k7::TWH, NPIX = k7::NPIX, DPW = k7::DPW, SLOT = k7::SLOT, ROWB = k7::ROWB, WB_OFF = k7::WB_OFF,
@@ -531,7 +520,7 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
     const int tap = i >> 6, ln = i & 63;
     const u32x4 v = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (unsigned)ln * 16u, ((tap * 2 + 1) * 2) * 1024, 0);
     const unsigned dst = WB_OFF + (unsigned)i * 16u;
-    CD_WR128(dst, v, 0);
+    ROWS_WR128(dst, v, 0);
   }
   float esc[8], esh[8];
 #pragma unroll
@@ -602,7 +591,7 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
   asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");   // this thread's share of the LDS-resident weights is written
   target(0);
 #pragma unroll
-  for (int i = 0; i < DPW; ++i) dma16(rs_src, d_voff[i], (unsigned)((w * DPW + i) * 1024));   // tile 0 -> slot 0
+  for (int i = 0; i < DPW; ++i) dma16<0>(rs_src, d_voff[i], (unsigned)((w * DPW + i) * 1024));   // tile 0 -> slot 0
   int cur = 0;
   for (int k = 0; k < cnt; ++k) {
     const unsigned sb = (unsigned)cur * SLOT;
@@ -616,14 +605,14 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
     u32x4 A[2][8], BL[7];
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
-      CD_RD128(t[it][0], a_pr, it * 2048);
-      CD_RD128(t[it][1], a_pr, it * 2048 + 16);
+      ROWS_RD128(t[it][0], a_pr, it * 2048);
+      ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
     }
 #pragma unroll
-    for (int r = 0; r < 8; ++r) CD_RD128(A[0][r], ad[0][0], r * ROWB);
+    for (int r = 0; r < 8; ++r) ROWS_RD128(A[0][r], ad[0][0], r * ROWB);
     target(k + 1);
 #pragma unroll
-    for (int i = 0; i < DPW; ++i) dma16(rs_src, d_voff[i], (unsigned)((cur ^ 1) * SLOT + (w * DPW + i) * 1024));
+    for (int i = 0; i < DPW; ++i) dma16<0>(rs_src, d_voff[i], (unsigned)((cur ^ 1) * SLOT + (w * DPW + i) * 1024));
     int pb, py0, px0;
     const bool pok = tile_of(k - 1, pb, py0, px0);
     auto mma = [&](auto gitag, auto dytag, auto jtag) {
@@ -646,10 +635,10 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
       if constexpr (gi + 1 < 14) {                         // the next group's operands: 8 A fragments (+ 7 B fragments of k-step 1)
         constexpr int dx1 = (gi + 1) >> 1, ks1 = (gi + 1) & 1;
 #pragma unroll
-        for (int r = 0; r < 8; ++r) CD_RD128(A[(gi + 1) & 1][r], ad[dx1][ks1], r * ROWB);
+        for (int r = 0; r < 8; ++r) ROWS_RD128(A[(gi + 1) & 1][r], ad[dx1][ks1], r * ROWB);
         if constexpr (ks1 == 1) {
 #pragma unroll
-          for (int dy = 0; dy < 7; ++dy) CD_RD128(BL[dy], a_wb, (dy * 7 + dx1) * 1024);
+          for (int dy = 0; dy < 7; ++dy) ROWS_RD128(BL[dy], a_wb, (dy * 7 + dx1) * 1024);
         }
       }
       // wait for THIS group's operands: everything but what was just issued (LDS operations complete in order)
@@ -686,7 +675,7 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
 #pragma unroll
       for (int r = 0; r < 16; ++r) {
         const float v = acc[j][r];
-        CD_WR32(a_pw, v, (j * 32 + (r & 3) + 8 * (r >> 2)) * 128);
+        ROWS_WR32(a_pw, v, (j * 32 + (r & 3) + 8 * (r >> 2)) * 128);
       }
     cur ^= 1;
   }
@@ -694,8 +683,8 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
   {
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
-      CD_RD128(t[it][0], a_pr, it * 2048);
-      CD_RD128(t[it][1], a_pr, it * 2048 + 16);
+      ROWS_RD128(t[it][0], a_pr, it * 2048);
+      ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
     }
     asm volatile("s_waitcnt lgkmcnt(0)"
                  : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1]), "+v"(t[2][0]), "+v"(t[2][1]), "+v"(t[3][0]), "+v"(t[3][1])::"memory");

@@ -1,17 +1,12 @@
 // The folded decomposition 1x1 (96 -> 32 over the virtual concat [x, HF1, HF2]) on 16-bit NHWC maps with plain 16-bit weights, as a
 // streaming LDS-DMA kernel.  Replaces conv_bf16x3_ws<1, 1, 4 | 12> (conv_mfma.hip) for that form: the persistent wave-specialised kernel
 // stages its input through registers (loader waves, VALU writes to LDS, two barriers per stage) although a stored 16-bit value IS the
-// MFMA operand.  Same data path as conv3x3_h16_dma (conv_dma.hip), minus everything a 1x1 does not need:
-//   * no halo, so nothing is shared between waves: a map is a run of B*H*W pixels x 64 B, a TILE is 64 consecutive pixels, and every
-//     wave streams its own tiles HBM -> LDS (buffer_load_dwordx4 ... lds, 16 B per lane) into a WAVE-PRIVATE ring: no s_barrier at all;
+// MFMA operand.  The wave-private data path of conv_rows.h (its rules on vmcnt and inline-asm LDS access, its operand swizzle and
+// park step), minus everything a 1x1 does not need:
+//   * no halo: a map is a run of B*H*W pixels x 64 B, a TILE is 64 consecutive pixels, and every wave streams its own tiles;
 //   * a ring slot is one source of one tile (4 KB = 4 DMA instructions); 4 slots, 3 in flight behind the one being read.  Two workgroups of
 //     4 waves per CU (two waves per SIMD: the B operand is 24 registers): 8 waves x 12 KB = 96 KB in flight per CU;
-//   * the 16-byte chunk a lane fetches is XOR-swizzled on the source side exactly as in conv3x3_h16_dma, so the A-operand ds_read_b128 of
-//     32 consecutive pixels is conflict-free;
-//   * the vector-memory pattern is fixed (4 DMAs per stage, 4 stores per tile, dead ones carry an out-of-range offset), so the
-//     s_waitcnt vmcnt(N) that retires a stage is a compile-time constant: N = the number of YOUNGER LOADS (stores do not retire in order
-//     with loads, conv_dma.hip Sched); every LDS access is inline asm (hipcc drains vmcnt in front of every LDS access it can see while
-//     an LDS-DMA is in flight);
+//   * the vector-memory pattern: 4 DMAs per stage, 4 stores per tile;
 //   * arithmetic as conv_ws_body<1, 1, ST> runs it: paif::mfma16<F> 32x32x16, sources in order, k-step 0 then 1, fp32 accumulation from
 //     zero; epilogue fma(acc, scale, shift) -> activation -> * alpha -> f32_to_h4<F>: the same instructions in the same order, so the
 //     same bits.
@@ -23,27 +18,23 @@
 #include <type_traits>
 
 #include "conv_dma.h"
-#include "paif_common.h"
+#include "conv_rows.h"
 
 namespace paif_conv_dma {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+using namespace paif_rows;
 
 constexpr int TP = 64;                        // pixels per tile
 constexpr int SLOT = TP * 64;                 // one source of a tile: 4 KB
 constexpr int DPS = SLOT / 1024;              // DMA instructions per stage (64 lanes x 16 B each)
 constexpr int NSLOT = 4, PF = NSLOT - 1;      // ring slots; stages in flight behind the one being read
-constexpr int PARK = 32 * 32 * 4;             // per-wave [32 px][32 ch] fp32 transposition buffer (one accumulator at a time)
 constexpr int WAVE_LDS = NSLOT * SLOT + PARK; // 20 KB
 constexpr int WAVES = 4;
 constexpr int LDS_BYTES = WAVES * WAVE_LDS;   // 80 KB: two workgroups per CU
 constexpr int GRID = 512;                     // persistent: 2 workgroups on each of 256 CUs
 static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU do not fit LDS");
 static_assert(PF == 3, "a stage's DMA target is the same source of the next tile: PF must equal the source count");
-constexpr unsigned RSRC_W3 = 0x00020000u;
-constexpr unsigned OOB = 0x80000000u;         // a byte offset no map reaches (checked at launch): the hardware returns 0 / drops the store
 
 #ifndef C1_LD_AUX
 #define C1_LD_AUX 2     // cache policy of the LDS-DMA loads: 2 = streaming (nt): every input byte is read exactly once; 0 = default
@@ -54,13 +45,6 @@ constexpr unsigned OOB = 0x80000000u;         // a byte offset no map reaches (c
                         // loads default / stores nt 115, loads nt / stores nt 110, loads nt / stores default 102, and the sum over
                         // all kernels of the step falls with it
 #endif
-#define C1_VMWAIT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-#define C1_RD128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#define C1_WR32(addr, val, off) asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(addr), "v"(val), "n"(off) : "memory")
-
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned lds_off) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)lds_off, 16, voff, 0, 0, C1_LD_AUX);
-}
 
 // F: 16-bit format of maps and weights (1 bf16, 2 fp16)
 template <int F>
@@ -105,14 +89,14 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv_h16_dma_1x1(Args a, int nt
 
   // ---- geometry of this lane ----
   // DMA instruction i of a stage moves chunk n = 64 i + l of the slot: pixel n >> 2, physical 16-byte chunk n & 3 = logical chunk ^ ((pixel >> 2) & 3)
-  const unsigned d_rel = (unsigned)((l >> 2) * 64 + (((l & 3) ^ ((l >> 4) & 3)) * 16));   // + 1024 i
+  const unsigned d_rel = ROWS_SWIZZLED(l >> 2, l & 3);                                    // + 1024 i
   const unsigned lds_w = (unsigned)(w * WAVE_LDS);                                        // this wave's ring; its park buffer behind it
   // A operand of pixel 32 sg + p, k-step ks: lane (pixel p, k half hh); (32 sg + p) >> 2 and p >> 2 agree mod 4: sg is an immediate offset
   unsigned a_rd[2];
 #pragma unroll
-  for (int ks = 0; ks < 2; ++ks) a_rd[ks] = lds_w + (unsigned)(p * 64 + (((2 * ks + hh) ^ ((p >> 2) & 3)) * 16));
-  const unsigned a_pw = lds_w + NSLOT * SLOT + (unsigned)((4 * hh * 32 + p) * 4);          // + ((r & 3) + 8 (r >> 2)) * 128
-  const unsigned a_pr = lds_w + NSLOT * SLOT + (unsigned)((l >> 2) * 128 + (l & 3) * 32);  // + it * 2048 (+ 16): pixel 16 it + (l >> 2), 8 channels
+  for (int ks = 0; ks < 2; ++ks) a_rd[ks] = lds_w + ROWS_SWIZZLED(p, 2 * ks + hh);
+  const unsigned a_pw = ROWS_PARK_WR_ADDR(lds_w + NSLOT * SLOT, p, hh);
+  const unsigned a_pr = ROWS_PARK_RD_ADDR(lds_w + NSLOT * SLOT, l);
   const unsigned e_lane = (unsigned)l * 16u;                                               // (pixel l >> 2, chunk l & 3) inside 16 pixels
 
   auto tile_byte = [&](int k) -> unsigned { return (unsigned)(gw + k * nw) * (unsigned)SLOT; };   // < 2^32: ntiles + nw tiles of 4 KB
@@ -129,7 +113,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv_h16_dma_1x1(Args a, int nt
   auto issue = [&](auto stag, int slot) {
     constexpr int S = decltype(stag)::value;
 #pragma unroll
-    for (int i = 0; i < DPS; ++i) dma16(rs_src[S], d_voff[i], lds_w + (unsigned)(slot * SLOT + i * 1024));
+    for (int i = 0; i < DPS; ++i) dma16<C1_LD_AUX>(rs_src[S], d_voff[i], lds_w + (unsigned)(slot * SLOT + i * 1024));
   };
 
   f32x16 acc[2];
@@ -138,15 +122,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv_h16_dma_1x1(Args a, int nt
   auto stage = [&](auto stag) {
     constexpr int S = decltype(stag)::value;
     issue(stag, (cur + PF) & (NSLOT - 1));
-    C1_VMWAIT(PF * DPS);
+    ROWS_VMWAIT(PF * DPS);
     const unsigned sb = (unsigned)cur * SLOT;
     u32x4 A[2][2];
     const unsigned ad0 = a_rd[0] + sb, ad1 = a_rd[1] + sb;
-    C1_RD128(A[0][0], ad0, 0);
-    C1_RD128(A[1][0], ad0, 32 * 64);
-    C1_RD128(A[0][1], ad1, 0);
-    C1_RD128(A[1][1], ad1, 32 * 64);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(A[0][0]), "+v"(A[1][0]), "+v"(A[0][1]), "+v"(A[1][1])::"memory");
+    ROWS_RD128(A[0][0], ad0, 0);
+    ROWS_RD128(A[1][0], ad0, 32 * 64);
+    ROWS_RD128(A[0][1], ad1, 0);
+    ROWS_RD128(A[1][1], ad1, 32 * 64);
+    ROWS_LGKMWAIT(0, "+v"(A[0][0]), "+v"(A[1][0]), "+v"(A[0][1]), "+v"(A[1][1]));
     __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
     for (int ks = 0; ks < 2; ++ks)
@@ -167,20 +151,11 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv_h16_dma_1x1(Args a, int nt
   // the finished tile k: each accumulator through the park buffer into [pixel][8 channels], epilogue, two 16-byte stores
   auto finish = [&](int k) {
     const unsigned tb = tile_byte(k);
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");       // MFMA result -> LDS-store data: wait states inline asm does not get
+    mfma_to_lds_wait();
 #pragma unroll
     for (int sg = 0; sg < 2; ++sg) {
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = acc[sg][r];
-        C1_WR32(a_pw, v, ((r & 3) + 8 * (r >> 2)) * 128);
-      }
       u32x4 t[2][2];
-      C1_RD128(t[0][0], a_pr, 0);                           // (LDS operations of a wave complete in order: the writes are in)
-      C1_RD128(t[0][1], a_pr, 16);
-      C1_RD128(t[1][0], a_pr, 2048);
-      C1_RD128(t[1][1], a_pr, 2048 + 16);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1])::"memory");
+      park_transpose(acc[sg], a_pw, a_pr, t);
 #pragma unroll
       for (int it = 0; it < 2; ++it) {
         float ev[8];
@@ -216,7 +191,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv_h16_dma_1x1(Args a, int nt
     stage(S2{});
     finish(k);
   }
-  C1_VMWAIT(0);            // no LDS-DMA may land after the workgroup's LDS is released
+  ROWS_VMWAIT(0);            // no LDS-DMA may land after the workgroup's LDS is released
 }
 
 }  // namespace

@@ -1,53 +1,35 @@
-// ECA block, conv2 = 3x3 dilation-1 32 -> 32 over PReLU(r) (fp16 NHWC-32 map, plain fp16 weights), run TWICE as a row-streaming LDS-DMA
-// kernel so that its output map is never stored: the POOL pass writes only the per-tile channel sums the gate is made of, the GATED pass
-// recomputes the conv and writes PReLU(fp16(o) * gate + r).  Replaces conv_mfma_bf16x3<3, 1, false, 14> + eca_apply_kernel<2> on large
-// fp16 maps (785 MB -> 472 MB per block).  Data path of conv3x3_h16_dma_rows (conv_dma_rows.hip), dilation 1:
-//   * a chain is (image, 32-column strip); a wave walks a RUN of consecutive rows downward, one warm-up row at each end, and shares
-//     nothing with any other wave: a wave-private LDS ring, no s_barrier anywhere.  Runs are whole 8-row tiles (paif_conv2d_blocks
-//     numbering), so one wave owns every pool partial it writes;
-//   * a ring slot is one source row piece, 34 pixels x 64 B, fetched by 3 DMA instructions with the source-side XOR swizzle of
-//     conv3x3_h16_dma; 5 slots (3 resident rows, 2 in flight); zero padding is the buffer descriptor's range check;
+// ECA block, conv2 = 3x3 dilation-1 32 -> 32 over PReLU(r) (fp16 NHWC-32 map, plain fp16 weights), run TWICE on the row-streaming LDS-DMA
+// body of conv_rows.h (halo 1) so that its output map is never stored: the POOL pass writes only the per-tile channel sums the gate is
+// made of, the GATED pass recomputes the conv and writes PReLU(fp16(o) * gate + r).  Replaces conv_mfma_bf16x3<3, 1, false, 14> +
+// eca_apply_kernel<2> on large fp16 maps (785 MB -> 472 MB per block).  What is this kernel's own:
+//   * a chain is (image, 32-column strip); runs are whole 8-row tiles (paif_conv2d_blocks numbering), so one wave owns every pool partial
+//     it writes;
 //   * INPUT PReLU ONCE PER ROW PIECE: when a piece has landed the wave rewrites it in place (3 x 16 B per lane, prelu_h2 below: the bits
 //     of conv_mfma_split_body's staging, fp16 -> fp32, v >= 0 ? v : slope * v, round to nearest even -> fp16) before its first use as an
-//     operand, in the shadow of the row's first six MFMAs; a piece feeds 9 fragment reads.  The GATED pass takes r (un-activated) from
-//     the piece BEFORE the rewrite, in the store layout, one row ahead of its use (two register sets);
-//   * every s_waitcnt vmcnt(N) is a compile-time count of younger loads; every LDS access is inline asm (the pool's cross-lane sums
-//     excepted: the compiler waits for its own);
-//   * arithmetic as conv_mfma_split_body<3, 1, false, 14> runs it: paif::mfma16<fp16>, tap = dy * 3 + dx ascending, k-step inner, fp32
-//     accumulation from zero, one MFMA per product.  POOL: epilogue_lds_n's summation tree (rows 2w, 2w + 1 of a tile form group w;
-//     lane (q, j) chains pixels it * 8 + j, it = 0..7, from 0.f; butterfly over j; ((g0 + g1) + g2) + g3).  GATED: eca_apply_kernel<2> on
-//     fp16(acc).  Same operations in the same order on every element, so the same bits as the three launches replaced.
+//     operand, through the hooks of conv_row(): in the shadow of the row's first six MFMAs; a piece feeds 9 fragment reads.  The GATED
+//     pass takes r (un-activated) from the piece BEFORE the rewrite, in the store layout, one row ahead of its use (two register sets);
+//   * the pool's cross-lane sums are the one LDS access that is not inline asm: the compiler waits for its own;
+//   * arithmetic as conv_mfma_split_body<3, 1, false, 14> runs it, one MFMA per product.  POOL: epilogue_lds_n's summation tree (rows
+//     2w, 2w + 1 of a tile form group w; lane (q, j) chains pixels it * 8 + j, it = 0..7, from 0.f; butterfly over j;
+//     ((g0 + g1) + g2) + g3).  GATED: eca_apply_kernel<2> on fp16(acc).  Same operations in the same order on every element, so the
+//     same bits as the three launches replaced.
 #include <stdint.h>
 #include <stdlib.h>
 
 #include <type_traits>
 
 #include "conv_eca_rows.h"
-#include "paif_common.h"
+#include "conv_rows.h"
 
 namespace paif_eca_rows {
 namespace {
 
-typedef float f32x16 __attribute__((ext_vector_type(16)));
-typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
-
-constexpr int RW = 32;                        // output columns of a strip
-constexpr int RWH = RW + 2;                   // source columns of a row piece
+using namespace paif_rows;
+typedef Ring<1> R;
+constexpr int RW = R::RW, DPS = R::DPS, SLOT = R::SLOT, NSLOT = R::NSLOT, PF = R::PF, WAVES = R::WAVES;
 constexpr int TR = 8;                         // rows of a pool tile
-constexpr int DPS = 3;                        // DMA instructions per row piece (64 lanes x 16 B each: 48 pixels, 34 live)
-constexpr int SLOT = DPS * 1024;
-constexpr int NSLOT = 5, PF = NSLOT - 3;      // ring slots: 3 resident rows + PF in flight
-constexpr int PARK = 32 * 32 * 4;             // per-wave [32 px][32 ch] fp32 transposition buffer
-constexpr int WAVE_LDS = NSLOT * SLOT + PARK; // 19 KB
-constexpr int WAVES = 4;
-constexpr int LDS_BYTES = WAVES * WAVE_LDS;   // 76 KB: two workgroups per CU
-constexpr int MAX_WAVES = 2048;               // 2 workgroups on each of 256 CUs
-constexpr int MIN_RUN = 2;                    // tiles (16 rows) per wave at least: the two warm-up rows cost at most 1/8
+constexpr int MIN_RUN = MIN_RUN_ROWS / TR;    // tiles per wave at least
 constexpr int N_ROW = PF * DPS;               // younger loads behind the DMAs of row t + 2 at the wait of step t
-static_assert(2 * LDS_BYTES <= 160 * 1024, "two workgroups per CU do not fit LDS");
-static_assert(RWH * 4 <= DPS * 64, "DMA instructions do not cover the row piece");
-constexpr unsigned RSRC_W3 = 0x00020000u;
-constexpr unsigned OOB = 0x80000000u;         // a byte offset no map reaches (checked at launch): the hardware returns 0 / drops the store
 
 #ifndef ER_LD_AUX_POOL
 #define ER_LD_AUX_POOL 0     // cache policy of the POOL pass's LDS-DMA loads: 0 = default (the GATED pass re-reads the map), 2 = streaming (nt)
@@ -58,15 +40,6 @@ constexpr unsigned OOB = 0x80000000u;         // a byte offset no map reaches (c
 #ifndef ER_ST_AUX
 #define ER_ST_AUX 0          // cache policy of the output stores (conv_h16_dma_1x1 and conv3x3_h16_dma_rows measured default best)
 #endif
-#define ER_VMWAIT(n) asm volatile("s_waitcnt vmcnt(%0)" ::"n"(n) : "memory")
-#define ER_RD128(dst, addr, off) asm volatile("ds_read_b128 %0, %1 offset:%2" : "=v"(dst) : "v"(addr), "n"(off) : "memory")
-#define ER_WR32(addr, val, off) asm volatile("ds_write_b32 %0, %1 offset:%2" ::"v"(addr), "v"(val), "n"(off) : "memory")
-#define ER_WR128(addr, val, off) asm volatile("ds_write_b128 %0, %1 offset:%2" ::"v"(addr), "v"(val), "n"(off) : "memory")
-
-template <int AUX>
-__device__ __forceinline__ void dma16(__amdgpu_buffer_rsrc_t rsrc, unsigned voff, unsigned lds_off) {
-  __builtin_amdgcn_raw_ptr_buffer_load_lds(rsrc, (__attribute__((address_space(3))) void*)(uintptr_t)lds_off, 16, voff, 0, 0, AUX);
-}
 
 // The input PReLU on stored fp16 values: the bits of f32_to_f16x4(prelu_f(float(x), slope)), the staging of conv_mfma_split_body, in 7
 // instructions per PAIR instead of the 11 of compare-and-select in fp32 (this rewrite shares the SIMD with the row's first six MFMAs):
@@ -96,7 +69,7 @@ __device__ __forceinline__ u32x4 prelu_h8(u32x4 v, float slope) {
 template <int MODE>
 __global__ __launch_bounds__(WAVES * 64, 2) void eca_conv2_rows(Args a, int total, int SX, int TY, int run) {
   constexpr int LD_AUX = MODE == POOL ? ER_LD_AUX_POOL : ER_LD_AUX_GATED;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
+  __shared__ __attribute__((aligned(16))) unsigned char smem[R::LDS_BYTES];
   asm volatile("" ::"v"((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem) : "memory");   // only asm touches it
 
   const int tid = threadIdx.x, l = tid & 63;
@@ -113,52 +86,32 @@ __global__ __launch_bounds__(WAVES * 64, 2) void eca_conv2_rows(Args a, int tota
   const __amdgpu_buffer_rsrc_t rs_out = __builtin_amdgcn_make_buffer_rsrc(MODE == POOL ? (void*)a.partial : a.out, 0,
                                                                           MODE == POOL ? a.B * TY * SX * 128 : map_bytes, RSRC_W3);
 
-  // ---- B operand: [tap][k-step], lane (n = l & 31, k = 8 (l >> 5) + j) -- the hi halves of the pack [tap][ks][hi|lo][64 lanes][16 B] ----
   u32x4 bw[9][2];
-  {
-    const __amdgpu_buffer_rsrc_t rs_w = __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(a.wpk), 0, 9 * 2 * 2 * 1024, RSRC_W3);
+  ROWS_LOAD_BW(bw, a.wpk, l)
 #pragma unroll
-    for (int tap = 0; tap < 9; ++tap)
-#pragma unroll
-      for (int ks = 0; ks < 2; ++ks) bw[tap][ks] = __builtin_amdgcn_raw_buffer_load_b128(rs_w, (unsigned)l * 16u, ((tap * 2 + ks) * 2) * 1024, 0);
-#pragma unroll
-    for (int tap = 0; tap < 9; ++tap) asm volatile("" : "+v"(bw[tap][0]), "+v"(bw[tap][1]));   // waited for HERE, not inside the row loop
-  }
+  for (int tap = 0; tap < 9; ++tap) asm volatile("" : "+v"(bw[tap][0]), "+v"(bw[tap][1]));   // waited for HERE, not inside the row loop
   float in_slope = *a.in_prelu;
   float slope = MODE == GATED ? *a.prelu : 0.f;
   asm volatile("" : "+v"(in_slope), "+v"(slope));
 
   // ---- geometry of this lane ----
-  // DMA instruction i moves chunk n = 64 i + l of the slot: piece column c = n >> 2, physical 16-byte chunk n & 3 = logical chunk ^ ((c >> 2) & 3)
   int d_col[DPS];
   unsigned d_rel[DPS];
-#pragma unroll
-  for (int i = 0; i < DPS; ++i) {
-    const int n = 64 * i + l, c = n >> 2;
-    d_col[i] = c;
-    d_rel[i] = (unsigned)(c * 64 + (((n & 3) ^ ((c >> 2) & 3)) * 16));
-  }
-  const unsigned lds_w = (unsigned)(w * WAVE_LDS);                                        // this wave's ring; its park buffer behind it
-  // A operand of output pixel p, horizontal tap dx, k-step ks: lane (pixel p, k half hh) reads piece column p + dx
+  ROWS_DMA_GEOMETRY(DPS, l, d_col, d_rel)
+  const unsigned lds_w = (unsigned)(w * R::WAVE_LDS);                                      // this wave's ring; its park buffer behind it
   unsigned a_rd[3][2];
-#pragma unroll
-  for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-    for (int ks = 0; ks < 2; ++ks) {
-      const int c = p + dx;
-      a_rd[dx][ks] = lds_w + (unsigned)(c * 64 + (((2 * ks + hh) ^ ((c >> 2) & 3)) * 16));
-    }
+  ROWS_A_ADDRS(1, lds_w, p, hh, a_rd)
   const unsigned a_rw = lds_w + (unsigned)l * 16u;                                         // the in-place rewrite: chunk 64 i + l, + i * 1024
-  const unsigned a_pw = lds_w + NSLOT * SLOT + (unsigned)((4 * hh * 32 + p) * 4);          // + ((r & 3) + 8 (r >> 2)) * 128
+  const unsigned a_pw = ROWS_PARK_WR_ADDR(lds_w + NSLOT * SLOT, p, hh);
   // park re-read.  POOL: virtual lane (j = l >> 3, q = l & 7) of epilogue_lds_n, pixel it * 8 + j, channel quad q (+ it * 1024).
-  // otherwise the store layout: pixel 16 it + (l >> 2), 8 channels (+ it * 2048 (+ 16))
-  const unsigned a_pr = lds_w + NSLOT * SLOT + (MODE == POOL ? (unsigned)((l >> 3) * 128 + (l & 7) * 16) : (unsigned)((l >> 2) * 128 + (l & 3) * 32));
+  // otherwise the store layout
+  const unsigned a_pr = MODE == POOL ? lds_w + NSLOT * SLOT + (unsigned)((l >> 3) * 128 + (l & 7) * 16) : ROWS_PARK_RD_ADDR(lds_w + NSLOT * SLOT, l);
   // the stored values of output pixel 16 it + (l >> 2), channels 8 (l & 3) ..: piece column 16 it + (l >> 2) + 1, logical chunk l & 3
   unsigned a_st[2];
 #pragma unroll
   for (int it = 0; it < 2; ++it) {
     const int c = 16 * it + (l >> 2) + 1;
-    a_st[it] = lds_w + (unsigned)(c * 64 + (((l & 3) ^ ((c >> 2) & 3)) * 16));
+    a_st[it] = lds_w + ROWS_SWIZZLED(c, l & 3);
   }
   const unsigned o_lane = (unsigned)l * 16u;                                               // (pixel l >> 2, chunk l & 3) inside 16 pixels of the output row
 
@@ -170,16 +123,16 @@ __global__ __launch_bounds__(WAVES * 64, 2) void eca_conv2_rows(Args a, int tota
   auto prelu_slot = [&](unsigned sb) {
     u32x4 v0, v1, v2;
     const unsigned ad = a_rw + sb;
-    ER_RD128(v0, ad, 0);
-    ER_RD128(v1, ad, 1024);
-    ER_RD128(v2, ad, 2048);
-    asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(v0), "+v"(v1), "+v"(v2)::"memory");
+    ROWS_RD128(v0, ad, 0);
+    ROWS_RD128(v1, ad, 1024);
+    ROWS_RD128(v2, ad, 2048);
+    ROWS_LGKMWAIT(0, "+v"(v0), "+v"(v1), "+v"(v2));
     v0 = prelu_h8(v0, in_slope);
     v1 = prelu_h8(v1, in_slope);
     v2 = prelu_h8(v2, in_slope);
-    ER_WR128(ad, v0, 0);
-    ER_WR128(ad, v1, 1024);
-    ER_WR128(ad, v2, 2048);
+    ROWS_WR128(ad, v0, 0);
+    ROWS_WR128(ad, v1, 1024);
+    ROWS_WR128(ad, v2, 2048);
   };
 
   while (pos < end) {
@@ -191,8 +144,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void eca_conv2_rows(Args a, int tota
     const int b = q / SX, sx = q - b * SX, x0 = sx * RW;
     pos += k;
     bool colok[DPS];
-#pragma unroll
-    for (int i = 0; i < DPS; ++i) colok[i] = d_col[i] < RWH && (unsigned)(x0 - 1 + d_col[i]) < (unsigned)W;
+    ROWS_COL_OK(R::RWH, 1, DPS, d_col, x0, W, colok)
     const bool xok0 = x0 + (l >> 2) < W, xok1 = x0 + 16 + (l >> 2) < W;
     bool xokp[4];
 #pragma unroll
@@ -209,100 +161,60 @@ __global__ __launch_bounds__(WAVES * 64, 2) void eca_conv2_rows(Args a, int tota
     // the DMAs of load m: row y0 - 1 + m into slot m % NSLOT (loads 0 .. n + 1 are the run; its first and last may lie outside the image)
     auto issue_row = [&](int m, int slot) {
       const int j = y0 - 1 + m;
-      const unsigned dead = (j >= 0 && j < H && m <= n + 1) ? 0u : OOB;              // (a scalar OR, not a branch around the DMAs)
-      const unsigned rowb = (unsigned)((b * H + j) * W + x0 - 1) * 64u;
-#pragma unroll
-      for (int i = 0; i < DPS; ++i) dma16<LD_AUX>(rs_src, (colok[i] ? rowb + d_rel[i] : OOB) | dead, lds_w + (unsigned)(slot * SLOT + i * 1024));
+      const unsigned dead = (j >= 0 && j < H && m <= n + 1) ? 0u : OOB;
+      const unsigned rowb = ROWS_ROW_BYTE(1, b * H + j, W, x0);
+      ROWS_ISSUE_ROW(LD_AUX, DPS, SLOT, rs_src, colok, d_rel, rowb, dead, lds_w, slot)
     };
 
     int cur = 0;             // ring slot of load t (the row above the output row)
     // Step t: output row y0 + t from loads t, t + 1, t + 2.  SET: t & 1.
     auto step = [&](auto settag, int t) {
       constexpr int SET = decltype(settag)::value;
-      const int s1 = cur + 1 >= NSLOT ? cur + 1 - NSLOT : cur + 1, s2 = cur + 2 >= NSLOT ? cur + 2 - NSLOT : cur + 2;
-      const int fill = cur == 0 ? NSLOT - 1 : cur - 1;   // = (t + 2 + PF) % NSLOT: the slot of load t - 1, read one step ago
-      issue_row(t + 2 + PF, fill);
-      ER_VMWAIT(N_ROW);                                  // load t + 2 has landed (and every older one)
-      const unsigned rb[3] = {(unsigned)(cur * SLOT), (unsigned)(s1 * SLOT), (unsigned)(s2 * SLOT)};
+      const Slots<NSLOT> sl(cur);
+      issue_row(t + 2 + PF, sl.fill);
+      ROWS_VMWAIT(N_ROW);                                  // load t + 2 has landed (and every older one)
+      const unsigned rb[3] = {(unsigned)(cur * SLOT), (unsigned)(sl.s1 * SLOT), (unsigned)(sl.s2 * SLOT)};
       // the new row piece (load t + 2): r of output row t + 1 out of it, then its PReLU in place -- in the shadow of the first tap row's MFMAs
       u32x4 n0, n1, n2;
       const unsigned nad = a_rw + rb[2];
-      ER_RD128(n0, nad, 0);
-      ER_RD128(n1, nad, 1024);
-      ER_RD128(n2, nad, 2048);
+      ROWS_RD128(n0, nad, 0);
+      ROWS_RD128(n1, nad, 1024);
+      ROWS_RD128(n2, nad, 2048);
       if constexpr (MODE == GATED) {
         const unsigned r0 = a_st[0] + rb[2], r1 = a_st[1] + rb[2];
-        ER_RD128(rawr[SET ^ 1][0], r0, 0);
-        ER_RD128(rawr[SET ^ 1][1], r1, 0);
+        ROWS_RD128(rawr[SET ^ 1][0], r0, 0);
+        ROWS_RD128(rawr[SET ^ 1][1], r1, 0);
       }
-      u32x4 A[2][3][2];       // [buffer][dx][ks]: the fragments of one vertical tap
-      auto read = [&](int buf, int dy) {
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) {
-            const unsigned ad = a_rd[dx][ks] + rb[dy];
-            ER_RD128(A[buf][dx][ks], ad, 0);
-          }
-      };
-      auto mma = [&](auto dytag) {
-        constexpr int dy = decltype(dytag)::value, buf = dy & 1;
-#pragma unroll
-        for (int dx = 0; dx < 3; ++dx)
-#pragma unroll
-          for (int ks = 0; ks < 2; ++ks) {
-            if (dy == 0 && dx == 0 && ks == 0) {         // first product of a row: C = 0
-              const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-              acc = paif::mfma16<2>(A[buf][dx][ks], bw[dy * 3 + dx][ks], z);
+      conv_row<2, 3>(
+          acc, a_rd, rb, bw,
+          [&] {                                             // the new piece (and r out of it) is in registers
+            if constexpr (MODE == GATED) {
+              ROWS_LGKMWAIT(12, "+v"(n0), "+v"(n1), "+v"(n2), "+v"(rawr[SET ^ 1][0]), "+v"(rawr[SET ^ 1][1]));
             } else {
-              acc = paif::mfma16<2>(A[buf][dx][ks], bw[dy * 3 + dx][ks], acc);
+              ROWS_LGKMWAIT(12, "+v"(n0), "+v"(n1), "+v"(n2));
             }
-          }
-      };
-      read(0, 0);
-      read(1, 1);
-      if constexpr (MODE == GATED) {
-        asm volatile("s_waitcnt lgkmcnt(12)" : "+v"(n0), "+v"(n1), "+v"(n2), "+v"(rawr[SET ^ 1][0]), "+v"(rawr[SET ^ 1][1])::"memory");
-      } else {
-        asm volatile("s_waitcnt lgkmcnt(12)" : "+v"(n0), "+v"(n1), "+v"(n2)::"memory");
-      }
-      asm volatile("s_waitcnt lgkmcnt(6)"
-                   : "+v"(A[0][0][0]), "+v"(A[0][0][1]), "+v"(A[0][1][0]), "+v"(A[0][1][1]), "+v"(A[0][2][0]), "+v"(A[0][2][1])::"memory");
-      __builtin_amdgcn_sched_barrier(0);
-      mma(std::integral_constant<int, 0>{});
-      n0 = prelu_h8(n0, in_slope);                        // (free to interleave with the six MFMAs above)
-      n1 = prelu_h8(n1, in_slope);
-      n2 = prelu_h8(n2, in_slope);
-      __builtin_amdgcn_sched_barrier(0);
-      ER_WR128(nad, n0, 0);                               // LDS operations of a wave complete in order: the reads below see the rewrite
-      ER_WR128(nad, n1, 1024);
-      ER_WR128(nad, n2, 2048);
-      read(0, 2);
-      asm volatile("s_waitcnt lgkmcnt(9)"
-                   : "+v"(A[1][0][0]), "+v"(A[1][0][1]), "+v"(A[1][1][0]), "+v"(A[1][1][1]), "+v"(A[1][2][0]), "+v"(A[1][2][1])::"memory");
-      __builtin_amdgcn_sched_barrier(0);
-      mma(std::integral_constant<int, 1>{});
-      __builtin_amdgcn_sched_barrier(0);
-      asm volatile("s_waitcnt lgkmcnt(0)"
-                   : "+v"(A[0][0][0]), "+v"(A[0][0][1]), "+v"(A[0][1][0]), "+v"(A[0][1][1]), "+v"(A[0][2][0]), "+v"(A[0][2][1])::"memory");
-      __builtin_amdgcn_sched_barrier(0);
-      mma(std::integral_constant<int, 2>{});
-      __builtin_amdgcn_sched_barrier(0);
+          },
+          [&] {
+            n0 = prelu_h8(n0, in_slope);
+            n1 = prelu_h8(n1, in_slope);
+            n2 = prelu_h8(n2, in_slope);
+          },
+          [&] {                                             // the 3 LDS operations of conv_row<.., 3>
+            ROWS_WR128(nad, n0, 0);
+            ROWS_WR128(nad, n1, 1024);
+            ROWS_WR128(nad, n2, 2048);
+          });
 
       // ---- the finished row: through the park buffer, then the pass's epilogue ----
-      asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");       // MFMA result -> LDS-store data: wait states inline asm does not get
-#pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = acc[r];
-        ER_WR32(a_pw, v, ((r & 3) + 8 * (r >> 2)) * 128);
-      }
+      mfma_to_lds_wait();
+      park_write(acc, a_pw);
       if constexpr (MODE == POOL) {
         u32x4 tq[4];
-        ER_RD128(tq[0], a_pr, 0);                             // (the writes are in: same wave, in order)
-        ER_RD128(tq[1], a_pr, 1024);
-        ER_RD128(tq[2], a_pr, 2048);
-        ER_RD128(tq[3], a_pr, 3072);
-        asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tq[0]), "+v"(tq[1]), "+v"(tq[2]), "+v"(tq[3])::"memory");
+        ROWS_RD128(tq[0], a_pr, 0);                             // (the writes are in: same wave, in order)
+        ROWS_RD128(tq[1], a_pr, 1024);
+        ROWS_RD128(tq[2], a_pr, 2048);
+        ROWS_RD128(tq[3], a_pr, 3072);
+        ROWS_LGKMWAIT(0, "+v"(tq[0]), "+v"(tq[1]), "+v"(tq[2]), "+v"(tq[3]));
         __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
         for (int it = 0; it < 4; ++it) {                      // pixels it * 8 + j of this row: elements 4 SET + it of the pair's chain
@@ -334,18 +246,15 @@ __global__ __launch_bounds__(WAVES * 64, 2) void eca_conv2_rows(Args a, int tota
         }
       } else {
         u32x4 tq[2][2];
-        ER_RD128(tq[0][0], a_pr, 0);
-        ER_RD128(tq[0][1], a_pr, 16);
-        ER_RD128(tq[1][0], a_pr, 2048);
-        ER_RD128(tq[1][1], a_pr, 2048 + 16);
+        park_read(tq, a_pr);
         u32x4 sv[2];                                           // STAGED: the operand row itself (load t + 1, rewritten a step ago)
         if constexpr (MODE == STAGED) {
           const unsigned c0 = a_st[0] + rb[1], c1 = a_st[1] + rb[1];
-          ER_RD128(sv[0], c0, 0);
-          ER_RD128(sv[1], c1, 0);
-          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tq[0][0]), "+v"(tq[0][1]), "+v"(tq[1][0]), "+v"(tq[1][1]), "+v"(sv[0]), "+v"(sv[1])::"memory");
+          ROWS_RD128(sv[0], c0, 0);
+          ROWS_RD128(sv[1], c1, 0);
+          ROWS_LGKMWAIT(0, ROWS_PARKED(tq), "+v"(sv[0]), "+v"(sv[1]));
         } else {
-          asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(tq[0][0]), "+v"(tq[0][1]), "+v"(tq[1][0]), "+v"(tq[1][1])::"memory");
+          ROWS_LGKMWAIT(0, ROWS_PARKED(tq));
         }
         __builtin_amdgcn_sched_barrier(0);
         const unsigned orow = (unsigned)((b * H + y0 + t) * W + x0) * 64u;
@@ -379,7 +288,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void eca_conv2_rows(Args a, int tota
         }
       }
       __builtin_amdgcn_sched_barrier(0);
-      cur = s1;
+      cur = sl.s1;
     };
 
     // ---- prologue: loads 0 .. 1 + PF into slots 0 .. 1 + PF; rows y0 - 1 and y0 are staged here, every later one by the step that waits for it ----
@@ -388,12 +297,12 @@ __global__ __launch_bounds__(WAVES * 64, 2) void eca_conv2_rows(Args a, int tota
     issue_row(1, 1);
     issue_row(2, 2);
     issue_row(3, 3);
-    ER_VMWAIT(2 * DPS);      // loads 0 and 1 have landed
+    ROWS_VMWAIT(2 * DPS);      // loads 0 and 1 have landed
     if constexpr (MODE == GATED) {
       const unsigned r0 = a_st[0] + SLOT, r1 = a_st[1] + SLOT;
-      ER_RD128(rawr[0][0], r0, 0);                            // r of output row 0 = load 1
-      ER_RD128(rawr[0][1], r1, 0);
-      asm volatile("s_waitcnt lgkmcnt(0)" : "+v"(rawr[0][0]), "+v"(rawr[0][1])::"memory");
+      ROWS_RD128(rawr[0][0], r0, 0);                            // r of output row 0 = load 1
+      ROWS_RD128(rawr[0][1], r1, 0);
+      ROWS_LGKMWAIT(0, "+v"(rawr[0][0]), "+v"(rawr[0][1]));
     }
     prelu_slot(0);
     prelu_slot(SLOT);
@@ -403,7 +312,7 @@ __global__ __launch_bounds__(WAVES * 64, 2) void eca_conv2_rows(Args a, int tota
       step(std::integral_constant<int, 1>{}, t + 1);
       if (t + 2 >= n) break;
     }
-    ER_VMWAIT(0);            // no LDS-DMA of this run may land in the next run's ring, or after the workgroup's LDS is released
+    ROWS_VMWAIT(0);            // no LDS-DMA of this run may land in the next run's ring, or after the workgroup's LDS is released
     asm volatile("s_waitcnt lgkmcnt(0)" ::: "memory");
   }
 }
@@ -412,9 +321,8 @@ template <int MODE>
 int launch_f(const Args& a, hipStream_t st, const char* what) {
   const int SX = (a.W + RW - 1) / RW, TY = (a.H + TR - 1) / TR;
   const int total = a.B * SX * TY;
-  const int per = (total + MAX_WAVES - 1) / MAX_WAVES;
-  const int run = per > MIN_RUN ? per : MIN_RUN;
-  const int waves = (total + run - 1) / run;
+  const Partition pt(total, MIN_RUN, R::MAX_WAVES);
+  const int run = pt.run, waves = pt.waves;
   hipLaunchKernelGGL((eca_conv2_rows<MODE>), dim3((waves + WAVES - 1) / WAVES), dim3(WAVES * 64), 0, st, a, total, SX, TY, run);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
@@ -438,8 +346,7 @@ bool fits(int B, int H, int W) {
 }
 
 bool by_size_rule(int B, int H, int W) {
-  // conv3x3_h16_dma_rows' rule: 16 rows and more on every one of the 2048 waves, and chains long enough to hold them
-  return fits(B, H, W) && H >= 64 && (long long)B * H * ((W + RW - 1) / RW) >= 32768;
+  return fits(B, H, W) && fills_chip(B, H, W);   // conv3x3_h16_dma_rows' rule
 }
 
 int launch(Mode m, const Args& a, hipStream_t st) {
