@@ -827,6 +827,36 @@ int paif_sdnet_dense_bwd(const float* pack, const float* feat, float* dfeat, int
 int paif_sdnet_stem_bwd(const float* pack, const float* feat, const float* dfeat, float* d_x1, float* d_x2, int B, int H, int W,
                         paif_stream_t stream);
 
+/* U2Fusion baseline (fusion_model/U2Fusion.py of the reference; csrc/u2fusion.hip).  fp32 throughout, NHWC maps: cat [B,H,W,264] holds
+ * conv_1's map and the five dense maps in the reference's cat order (44 channels each), s1 [B,H,W,128], s2 [B,H,W,64], s3 [B,H,W,32]
+ * are the maps of sub.0 .. sub.2; the gradient buffers d_cat, d_s1, d_s2, d_s3 use the same layouts.  Layers: 0 conv_1, 1..5
+ * dense_layers.0..4, 6..8 sub.0..2, 9 sub.3.  x_over / x_under are addressed as plane b at x + b * sb (floats); every other plane is
+ * dense [B,H,W].  pack: paif_u2fusion_pack_floats() floats, written by ten paif_u2fusion_pack_conv calls.  No host synchronisation, no
+ * allocation: capturable.  Bit-reproducible (no atomics). */
+size_t paif_u2fusion_pack_floats(void);
+/* One Conv2d's weight [cout,cin,3,3] and bias into the kernels' layout; layers 1..8 in MFMA operand order, forward and transposed. */
+int paif_u2fusion_pack_conv(const float* w, const float* b, int layer, float* pack, paif_stream_t stream);
+/* fusion_model/U2Fusion.py:121-122: channels [0, 44) of cat = LeakyReLU(0.2)(conv 3x3, pad 1, 2 -> 44) of the two planes. */
+int paif_u2fusion_stem_fwd(const float* x_over, size_t sb1, const float* x_under, size_t sb2, const float* pack, float* cat, int B, int H,
+                           int W, paif_stream_t stream);
+/* fusion_model/U2Fusion.py:96-98, :114-116: layer 1..8 = LeakyReLU(0.2)(conv 3x3, pad 1), an implicit GEMM on v_mfma_f32_16x16x4_f32.
+ * Layers 1..5: in = out = cat, reads channels [0, 44 * layer), writes [44 * layer, 44 * (layer + 1)).  6: cat -> s1, 7: s1 -> s2,
+ * 8: s2 -> s3. */
+int paif_u2fusion_conv_fwd(const float* pack, int layer, const float* in, float* out, int B, int H, int W, paif_stream_t stream);
+/* fusion_model/U2Fusion.py:117-118: fused = tanh(conv 3x3, pad 1, 32 -> 1) of s3. */
+int paif_u2fusion_head_fwd(const float* pack, const float* s3, float* fused, int B, int H, int W, paif_stream_t stream);
+/* Reverse of sub.3: dy = d_fused * (1 - fused^2) through the transposed conv; WRITES d_s3. */
+int paif_u2fusion_head_bwd(const float* pack, const float* fused, const float* d_fused, float* d_s3, int B, int H, int W,
+                           paif_stream_t stream);
+/* Reverse of layer 1..8 (input gradients): through the LeakyReLU (branch from the taped output, out > 0) and the transposed conv.
+ * 8: taped s3, d_s3 -> d_s2 (written); 7: s2, d_s2 -> d_s1 (written); 6: s1, d_s1 -> all 264 channels of d_cat (written); 5..1:
+ * taped = cat, d_out = d_in = d_cat: channels [44 * layer, 44 * (layer + 1)) are read and ADDED into [0, 44 * layer).  In that order. */
+int paif_u2fusion_conv_bwd(const float* pack, int layer, const float* taped, const float* d_out, float* d_in, int B, int H, int W,
+                           paif_stream_t stream);
+/* Reverse of conv_1: channels [0, 44) of d_cat through the LeakyReLU and the transposed conv -> d_x_over, d_x_under (written). */
+int paif_u2fusion_stem_bwd(const float* pack, const float* cat, const float* d_cat, float* d_x_over, float* d_x_under, int B, int H, int W,
+                           paif_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -217,6 +217,14 @@ SIGNATURES = {
     "paif_sdnet_fuse_bwd": (c_int, [F, F, F, F, c_int, c_int, c_int, F]),
     "paif_sdnet_dense_bwd": (c_int, [F, F, F, c_int, c_int, c_int, c_int, F]),
     "paif_sdnet_stem_bwd": (c_int, [F, F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_u2fusion_pack_floats": (c_size_t, []),
+    "paif_u2fusion_pack_conv": (c_int, [F, F, c_int, F, F]),
+    "paif_u2fusion_stem_fwd": (c_int, [F, c_size_t, F, c_size_t, F, F, c_int, c_int, c_int, F]),
+    "paif_u2fusion_conv_fwd": (c_int, [F, c_int, F, F, c_int, c_int, c_int, F]),
+    "paif_u2fusion_head_fwd": (c_int, [F, F, F, c_int, c_int, c_int, F]),
+    "paif_u2fusion_head_bwd": (c_int, [F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_u2fusion_conv_bwd": (c_int, [F, c_int, F, F, F, c_int, c_int, c_int, F]),
+    "paif_u2fusion_stem_bwd": (c_int, [F, F, F, F, F, c_int, c_int, c_int, F]),
 }
 
 _lib = None

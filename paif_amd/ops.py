@@ -2275,3 +2275,50 @@ def sdnet_backward(feat, out, d_out, pack):
         _lib.check(L.paif_sdnet_dense_bwd(_p(pack), _p(feat), _p(dfeat), level, B, H, W, _stream()), "sdnet_dense_bwd")
     _lib.check(L.paif_sdnet_stem_bwd(_p(pack), _p(feat), _p(dfeat), _p(d1), _p(d2), B, H, W, _stream()), "sdnet_stem_bwd")
     return d1, d2
+
+
+# ---------------------------------------------------------------------------------------------
+# U2Fusion baseline (csrc/u2fusion.hip; fusion_model/u2fusion.py is the module)
+# ---------------------------------------------------------------------------------------------
+def u2fusion_pack(convs):
+    """convs: the ten (weight, bias) in layer order -- conv_1, dense_layers.0..4, sub.0..3 -> the kernels' weight layout (layers 1..8 in
+    MFMA operand order, forward and transposed)."""
+    dev = convs[0][0].device
+    pack = torch.zeros(lib().paif_u2fusion_pack_floats(), device=dev, dtype=torch.float32)
+    for layer, (w, b) in enumerate(convs):
+        _lib.check(lib().paif_u2fusion_pack_conv(_p(w.detach().contiguous()), _p(b.detach().contiguous()), layer, _p(pack), _stream()),
+                   "u2fusion_pack_conv")
+    return pack
+
+
+def u2fusion_forward(x_over, x_under, pack):
+    """Two [B,1,H,W] planes -> ((cat [B,H,W,264], s1 [B,H,W,128], s2 [B,H,W,64], s3 [B,H,W,32]): the nine LeakyReLU maps, NHWC;
+    fused [B,1,H,W]).  Ten launches."""
+    B, _, H, W = x_over.shape
+    x_over, p1, s1_ = _plane(x_over)
+    x_under, p2, s2_ = _plane(x_under)
+    L = lib()
+    dev = x_over.device
+    cat, s1, s2, s3 = (torch.empty((B, H, W, c), device=dev, dtype=torch.float32) for c in (264, 128, 64, 32))
+    fused = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    _lib.check(L.paif_u2fusion_stem_fwd(p1, s1_, p2, s2_, _p(pack), _p(cat), B, H, W, _stream()), "u2fusion_stem_fwd")
+    for layer, src, dst in ((1, cat, cat), (2, cat, cat), (3, cat, cat), (4, cat, cat), (5, cat, cat), (6, cat, s1), (7, s1, s2), (8, s2, s3)):
+        _lib.check(L.paif_u2fusion_conv_fwd(_p(pack), layer, _p(src), _p(dst), B, H, W, _stream()), "u2fusion_conv_fwd")
+    _lib.check(L.paif_u2fusion_head_fwd(_p(pack), _p(s3), _p(fused), B, H, W, _stream()), "u2fusion_head_fwd")
+    return (cat, s1, s2, s3), fused
+
+
+def u2fusion_backward(cat, s1, s2, s3, fused, d_fused, pack):
+    """Reverse of u2fusion_forward (input gradients) from the taped maps and fused plane -> (d_x_over, d_x_under) [B,1,H,W].  Ten launches;
+    nothing is recomputed and nothing needs a memset."""
+    B, _, H, W = fused.shape
+    L = lib()
+    d_fused = d_fused.contiguous()
+    d_cat, d_s1, d_s2, d_s3 = (torch.empty_like(m) for m in (cat, s1, s2, s3))
+    d1, d2 = torch.empty_like(fused), torch.empty_like(fused)
+    _lib.check(L.paif_u2fusion_head_bwd(_p(pack), _p(fused), _p(d_fused), _p(d_s3), B, H, W, _stream()), "u2fusion_head_bwd")
+    for layer, taped, d_out, d_in in ((8, s3, d_s3, d_s2), (7, s2, d_s2, d_s1), (6, s1, d_s1, d_cat), (5, cat, d_cat, d_cat), (4, cat, d_cat, d_cat),
+                                      (3, cat, d_cat, d_cat), (2, cat, d_cat, d_cat), (1, cat, d_cat, d_cat)):
+        _lib.check(L.paif_u2fusion_conv_bwd(_p(pack), layer, _p(taped), _p(d_out), _p(d_in), B, H, W, _stream()), "u2fusion_conv_bwd")
+    _lib.check(L.paif_u2fusion_stem_bwd(_p(pack), _p(cat), _p(d_cat), _p(d1), _p(d2), B, H, W, _stream()), "u2fusion_stem_bwd")
+    return d1, d2

@@ -138,6 +138,25 @@ def load_formula_weights(module, salt=0, strict=True, head=None):
     return module
 
 
+# The ten convs of the U2Fusion baseline (reference fusion_model/U2Fusion.py:102-118) as (state_dict prefix, out channels, in channels):
+# its 658,728 weights would not fit a committed fixture, so the fixtures store one fp32 scale per conv and one shift of the last bias.
+U2FUSION_CONVS = ((("conv_1.0", 44, 2),) + tuple(("dense_layers.%d.conv.0" % i, 44, 44 * (i + 1)) for i in range(5))
+                  + (("sub.0.0", 128, 264), ("sub.1.0", 64, 128), ("sub.2.0", 32, 64), ("sub.3", 1, 32)))
+
+
+def u2fusion_state_dict(scales, shift):
+    """key -> float32 numpy array: formula_tensor("u2/" + key) times the conv's scale (weight and bias alike), `shift` added to
+    sub.3.bias.  tools/make_golden_u2fusion.py and the tests rebuild the fixture weights with this one expression."""
+    scales = np.asarray(scales, dtype=np.float32)
+    assert scales.shape == (len(U2FUSION_CONVS),)
+    sd = {}
+    for (name, cout, cin), s in zip(U2FUSION_CONVS, scales):
+        sd[name + ".weight"] = formula_tensor("u2/" + name + ".weight", (cout, cin, 3, 3)) * s
+        sd[name + ".bias"] = formula_tensor("u2/" + name + ".bias", (cout,)) * s
+    sd["sub.3.bias"] = sd["sub.3.bias"] + np.float32(shift)
+    return sd
+
+
 # --------------------------------------------------------------------------------------
 # inputs
 # --------------------------------------------------------------------------------------
