@@ -39,6 +39,14 @@ constexpr int TW = 32, TH = 8;          // output tile
 #ifndef CD_ST_AUX
 #define CD_ST_AUX 2   // cache policy of the output stores: 2 = streaming (nt); 0 = default (A/B: tools/build_variant1.sh ... -DCD_ST_AUX=0)
 #endif
+#ifndef CD_EPI_SWAP
+#define CD_EPI_SWAP 1 // epilogue of the kernels without a fused ChannelPool: 1 = pixel-per-lane accumulators and the half-wave swap of conv_rows.h
+                      // (no LDS park); 0 = the park epilogue everywhere (A/B: tools/build_variant1.sh ... -DCD_EPI_SWAP=0)
+#endif
+#ifndef CD_EPI_LINES
+#define CD_EPI_LINES 1 // swap epilogue: 1 = a second exchange (v_permlane16_swap) so that a store instruction writes 16 whole 64-byte pixels, as the
+                      // park epilogue's stores do; 0 = a store instruction writes 32 bytes of each of 32 pixels
+#endif
 #ifndef CD_EXP
 #define CD_EXP 0      // experiments (timing only, wrong results): 1 no stores, 2 no MFMAs, 4 no HBM reads (every DMA lane out of range)
 #endif
@@ -54,9 +62,9 @@ struct Geo {
   static constexpr int PF = DIL == 1 ? CD_PF : 3;             // stages in flight ahead of the MFMAs
   static constexpr int NSLOT = PF + 1;
   static constexpr int ROWB = TWH * 64;                       // one halo row in LDS
-  static constexpr int PARK_OFF = NSLOT * SLOT;               // the transposition buffers behind the ring
-  static constexpr int LDS_BYTES = PARK_OFF + 4 * PARK_WAVE;
-  static_assert(LDS_BYTES <= 160 * 1024, "ring + transposition buffers exceed LDS");
+  static constexpr int PARK_OFF = NSLOT * SLOT;               // the transposition buffers behind the ring (park epilogue only)
+  static constexpr int lds_bytes(bool parked) { return PARK_OFF + (parked ? 4 * PARK_WAVE : 0); }
+  static_assert(lds_bytes(true) <= 160 * 1024, "ring + transposition buffers exceed LDS");
   static_assert(4 * DPW * 64 >= NPIX * 4, "DMA instructions do not cover the halo tile");
   // the wave's two output rows are `base` and `base + DIL`: their 3 vertical taps read input rows base + DIL * {0, 1, 2, 3} -- four
   // fragments feed six MFMAs at either dilation (rows 2 w, 2 w + 1 would need six fragments at dilation 2)
@@ -98,8 +106,17 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
   typedef Geo<DIL> G;
   constexpr int TWH = G::TWH, NPIX = G::NPIX, DPW = G::DPW, SLOT = G::SLOT, PF = G::PF, NSLOT = G::NSLOT, ROWB = G::ROWB, PARK_OFF = G::PARK_OFF;
   typedef Sched<NSRC, NRES, PF, DPW> SC;
-  constexpr int U = SC::U, D = SC::D;
-  __shared__ __attribute__((aligned(16))) unsigned char smem[G::LDS_BYTES];
+  // SW: the swap epilogue (conv_rows.h).  The MFMAs take (weights, pixels), so a lane holds ONE PIXEL's channels 8 g + 4 hh + i, and the
+  // finished tile stays in its accumulators while the next tile's first stage runs: two accumulator sets alternate per tile (set K & 1
+  // of tile K of the unrolled loop: the unroll factor, = the number of residual sets, is rounded up to even; dilation 2 goes from 3
+  // to 4).  On the park epilogue stay the fused ChannelPool (CP: its fp32 sum is a DPP quad tree over the parked layout) and the two
+  // forms whose registers do not hold the second accumulator set and the 16 more epilogue constants (hipcc spills inside the tile
+  // loop): three sources with three residual maps (216 registers of weights + 96 of residual sets) and dilation 2 with three
+  // residual maps (4 sets of 48).
+  constexpr bool SW = CD_EPI_SWAP && !CP && !(NRES == 3 && (NSRC == 3 || DIL == 2));
+  constexpr int U = SW ? (SC::U + 1) & ~1 : SC::U, D = SC::D;
+  constexpr int NACC = SW ? 2 : 1;
+  __shared__ __attribute__((aligned(16))) unsigned char smem[G::lds_bytes(!SW)];
   asm volatile("" ::"v"((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem) : "memory");   // only asm touches it
 
   const int tid = threadIdx.x, l = tid & 63;
@@ -159,10 +176,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
   }
   // epilogue constants in the [pixel][8 channels] layout a lane stores: channels 8 (l & 3) + j.  act(z) * alpha = act(alpha z)
   // for alpha > 0 (checked at launch), and every activation is  max(z, 0) + slope * min(z, 0)  (none: slope 1, ReLU: slope 0)
-  float esc[8], esh[8];
+  // SW: the lane's 16 channels in accumulator-register order, channel 8 (r >> 2) + 4 hh + (r & 3)
+  constexpr int NEC = SW ? 16 : 8;
+  float esc[NEC], esh[NEC];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = 8 * (l & 3) + j;
+  for (int j = 0; j < NEC; ++j) {
+    const int c = SW ? ROWS_ACC_CHANNEL(j, hh) : 8 * (l & 3) + j;
     esc[j] = ((a.scale && c < a.cout) ? a.scale[c] : 1.f) * a.alpha;
     esh[j] = ((a.shift && c < a.cout) ? a.shift[c] : 0.f) * a.alpha;
   }
@@ -206,8 +225,14 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
   const unsigned a_pr = PARK_OFF + w * PARK_WAVE + (l >> 2) * 128 + (l & 3) * 32;   // + it * 2048 (+ 16): pixel 16 it + (l >> 2), 8 channels
   const unsigned e_lane = (unsigned)l * 16u;                                      // (pixel l >> 2, chunk l & 3) inside 16 pixels of a 32-channel map
   const unsigned o_lane = 8 * (l & 3) < a.cout ? (unsigned)((l >> 2) * opitch + (l & 3) * 16) : OOB;   // the same in the OUTPUT map
+  // SW: 16-byte access `it` = (row it >> 1, channel half it & 1): lane l at pixel p, byte 32 (it & 1) + 16 hh of the pixel
+  const unsigned e_lane_sw = (unsigned)(p * 64 + hh * 16);
+  const unsigned o_lane_sw = (unsigned)(p * opitch + hh * 16);
+  // CD_EPI_LINES: behind line_swap() store s carries pixel 16 s + (l & 15), byte 32 (row & 1) + 16 (row >> 1), row = l >> 4 (rows 1 and 3
+  // hold channels 16 .. 31: dead with 16 output channels)
+  const unsigned o_lane_ln = ((l >> 4) & 1) * 16 < a.cout ? (unsigned)((l & 15) * opitch + ((l >> 4) & 1) * 32 + (l >> 5) * 16) : OOB;
 
-  // residual maps of a tile (this wave's 2 rows): 4 x 16 B per lane and map
+  // residual maps of a tile (this wave's 2 rows): 4 x 16 B per lane and map (SW: in the stored layout; epi() brings them to the accumulator's)
   u32x4 rr[U][NRES > 0 ? NRES : 1][4];
   auto issue_res = [&](auto settag, int k) {
     constexpr int SET = decltype(settag)::value;
@@ -215,11 +240,12 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
     const bool ok = tile_of(k, b, y0, x0);
 #pragma unroll
     for (int it = 0; it < 4; ++it) {
-      const int y = y0 + wb + (it >> 1) * DIL, x = x0 + (it & 1) * 16 + (l >> 2);
+      const int y = y0 + wb + (it >> 1) * DIL, x = SW ? x0 + p : x0 + (it & 1) * 16 + (l >> 2);
       const bool in = ok && y < H && x < W;
-      const unsigned soff = (unsigned)(((b * H + y) * W + x0 + (it & 1) * 16) * 64);
+      const unsigned soff = SW ? (unsigned)(((b * H + y) * W + x0) * 64 + (it & 1) * 32) : (unsigned)(((b * H + y) * W + x0 + (it & 1) * 16) * 64);
+      const unsigned voff = in ? (SW ? e_lane_sw : e_lane) : OOB;
 #pragma unroll
-      for (int r = 0; r < NRES; ++r) rr[SET][r][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_res[r], in ? e_lane : OOB, soff, 0);
+      for (int r = 0; r < NRES; ++r) rr[SET][r][it] = __builtin_amdgcn_raw_buffer_load_b128(rs_res[r], voff, soff, 0);
     }
   };
 
@@ -229,18 +255,23 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
     const s16x8 z = {0, 0, 0, 0, 0, 0, 0, 0};
     f = __builtin_bit_cast(u32x4, __builtin_elementwise_max(__builtin_bit_cast(s16x8, f), z));
   };
-  f32x16 acc[2];
-  u32x4 t[4][2];          // a finished tile, transposed: [16-pixel group][channels 0-3 | 4-7 of the lane's 8] fp32 bits
+  f32x16 acc[NACC][2];    // [set][output row]; park epilogue: one set
+  if constexpr (SW) {     // the first tile's stage 0 runs the (dropped) epilogue of "tile -1" out of set 1
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[1][0][r] = acc[1][1][r] = 0.f;
+  }
+  u32x4 t[4][2];          // park epilogue: a finished tile, transposed: [16-pixel group][channels 0-3 | 4-7 of the lane's 8] fp32 bits
 #pragma unroll
   for (int it = 0; it < 4; ++it) t[it][0] = t[it][1] = u32x4{0, 0, 0, 0};
-  float ev[8];
+  float ev[8];            // SW: only ev[0], the even channel of the open pair
+  u32x4 oq[2];            // SW: the two 16-byte pieces of the open pixel row: packed pair by pair, swapped in micro-step 16, stored in 17
   float pmx = 0.f, psm = 0.f;   // CP: running (max, sum) of the lane's 8 channels of one pixel
   int cur = NSLOT - PF;    // ring slot of the current stage; the prologue's virtual stages -PF .. -1 bring it to 0
 
   // Epilogue micro-step m = 9 it + j of the tile in `t` (coordinates pb, py0, px0; residual set SETP): j < 8 one channel of the
   // lane's 8 -- scale / shift, activation, residual maps --, j == 8 the bf16 pack and the 16-byte store of pixel group `it`.
   // A handful of VALU instructions each: they run in the shadow of the MFMA they are placed behind.
-  auto epi = [&](auto mtag, auto settag, bool pok, int pb, int py0, int px0) {
+  auto epi_park = [&](auto mtag, auto settag, bool pok, int pb, int py0, int px0) {
     constexpr int M = decltype(mtag)::value, SETP = decltype(settag)::value;
     constexpr int it = M / 9, j = M % 9;
     if constexpr (j < 8) {
@@ -279,12 +310,62 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
       }
     }
   };
+  // The same 36 slots under the swap epilogue, m = 18 row + q of the tile in accumulator set AP: a lane owns pixel p of the wave's two
+  // rows.  q < 16: the channel of accumulator register q (group g = q >> 2: store piece it = 2 row + (g >> 1), 16 bytes of the pixel);
+  // the first channel of a piece also brings its residual maps from the stored layout to the accumulator's, in place (2 swaps per
+  // map); an odd channel packs its pair to 16 bits (f32_to_h4's conversion, pair by pair).
+  // q == 16: the 4 swaps of the row; q == 17: its two 16-byte stores, back to back (one 64-byte pixel line).
+  auto epi_swap = [&](auto mtag, auto settag, auto aptag, bool pok, int pb, int py0, int px0) {
+    constexpr int M = decltype(mtag)::value, SETP = decltype(settag)::value, AP = decltype(aptag)::value;
+    constexpr int row = M / 18, q = M % 18;
+    if constexpr (q < 16) {
+      constexpr int it = 2 * row + (q >> 3), j = q & 7;   // the piece, and the channel's place in it (as in epi_park)
+      if constexpr (j == 0) {
+#pragma unroll
+        for (int r = 0; r < NRES; ++r) rr[SETP][r][it] = swap_unpack(rr[SETP][r][it]);
+      }
+      float v = __builtin_fmaf(acc[AP][row][q], esc[q], esh[q]);
+      v = __builtin_fmaf(e_slope, fminf(v, 0.f), fmaxf(v, 0.f));
+#pragma unroll
+      for (int r = 0; r < NRES; ++r) {
+        const unsigned u = rr[SETP][r][it][j >> 1];
+        if constexpr (F == 2) v += (float)__builtin_bit_cast(paif::f16x2_t, u)[j & 1];
+        else v += __uint_as_float((j & 1) ? (u & 0xffff0000u) : (u << 16));
+      }
+      if constexpr ((j & 1) == 0) ev[0] = v;
+      else oq[q >> 3][j >> 1] = f32_to_h2<F>(ev[0], v);
+    } else if constexpr (q == 16) {
+      oq[0] = swap_unpack(oq[0]);                         // = the swap of its two packed groups
+      oq[1] = swap_unpack(oq[1]);
+      if constexpr (CD_EPI_LINES) line_swap(oq[0], oq[1]);
+    } else {
+      const int y = py0 + wb + row * DIL;
+      const unsigned soff = (unsigned)(((pb * H + y) * W + px0) * opitch);
+      const bool ok = !(CD_EXP & 1) && pok && y < H;
+      if constexpr (CD_EPI_LINES) {
+        const int x = px0 + (l & 15);
+        __builtin_amdgcn_raw_buffer_store_b128(oq[0], rs_out, (ok && x < W) ? o_lane_ln : OOB, soff, CD_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(oq[1], rs_out, (ok && x + 16 < W) ? o_lane_ln : OOB, soff + (unsigned)(16 * opitch), CD_ST_AUX);
+      } else {
+        const int x = px0 + p;
+        // 16 output channels (32-byte pixels): the piece of channels 16 .. 31 is dropped
+        __builtin_amdgcn_raw_buffer_store_b128(oq[0], rs_out, (ok && x < W) ? o_lane_sw : OOB, soff, CD_ST_AUX);
+        __builtin_amdgcn_raw_buffer_store_b128(oq[1], rs_out, (ok && x < W && a.cout > 16) ? o_lane_sw + 32u : OOB, soff, CD_ST_AUX);
+      }
+      asm volatile("s_nop 2" : "+v"(oq[0]), "+v"(oq[1]));   // 128-bit store data: WAR hazard hipcc does not pad
+    }
+  };
+  auto epi = [&](auto mtag, auto settag, auto aptag, bool pok, int pb, int py0, int px0) {
+    if constexpr (SW) epi_swap(mtag, settag, aptag, pok, pb, py0, px0);
+    else epi_park(mtag, settag, pok, pb, py0, px0);
+  };
 
   // One stage.  VIRT: a stage in front of the first tile -- only its vector-memory pattern is issued (stores dropped).
   auto stage = [&](auto ktag, auto stag, auto virt, int k) {
     constexpr int K = decltype(ktag)::value, S = decltype(stag)::value;
     constexpr bool VIRT = decltype(virt)::value;
     constexpr int SETP = (K + U - 1) % U;                 // residual set of the previous tile
+    constexpr int AC = SW ? K & 1 : 0, AP = SW ? AC ^ 1 : 0;   // accumulator sets of this tile and of the previous one (U is even)
     const unsigned sb = (unsigned)cur * SLOT;
     const int fill = cur == 0 ? NSLOT - 1 : cur - 1;      // = (cur + PF) % NSLOT: the slot read one stage ago
     u32x4 A[2][4];
@@ -296,7 +377,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
       for (int dx = 0; dx < 3; ++dx)
 #pragma unroll
         for (int ks = 0; ks < 2; ++ks) ad[dx][ks] = a_rd[dx][ks] + sb;
-      if constexpr (S == 0) {                              // read the previous tile back from its transposition buffer, [pixel][channel]
+      if constexpr (S == 0 && !SW) {                       // read the previous tile back from its transposition buffer, [pixel][channel]
 #pragma unroll
         for (int it = 0; it < 4; ++it) {
           ROWS_RD128(t[it][0], a_pr, it * 2048);
@@ -328,15 +409,18 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
         constexpr int gi = decltype(gitag)::value, dy = decltype(dytag)::value, j = decltype(jtag)::value;
         constexpr int ks = gi / 3, dx = gi % 3;
         if constexpr (!((CD_EXP & 2) && (dy > 0 || j > 0))) {
-          const u32x4 av = A[gi & 1][j + dy], bv = bw[S][dy * 3 + dx][ks];
+          // (pixels, weights): a lane holds one channel of 16 pixels (what the park takes); SW: (weights, pixels), one pixel's 16 channels
+          const u32x4 pv = A[gi & 1][j + dy], wv = bw[S][dy * 3 + dx][ks];
+          const u32x4 av = SW ? wv : pv, bv = SW ? pv : wv;
           if constexpr (S == 0 && gi == 0 && dy == 0) {    // first product of a tile: C = 0
             const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-            acc[j] = paif::mfma16<F>(av, bv, z);
+            acc[AC][j] = paif::mfma16<F>(av, bv, z);
           } else {
-            acc[j] = paif::mfma16<F>(av, bv, acc[j]);
+            acc[AC][j] = paif::mfma16<F>(av, bv, acc[AC][j]);
           }
         }
-        if constexpr (S == 0) epi(std::integral_constant<int, gi * 6 + dy * 2 + j>{}, std::integral_constant<int, SETP>{}, pok, pb, py0, px0);
+        if constexpr (S == 0)
+          epi(std::integral_constant<int, gi * 6 + dy * 2 + j>{}, std::integral_constant<int, SETP>{}, std::integral_constant<int, AP>{}, pok, pb, py0, px0);
         if constexpr (IA == 2) {      // the fragment the NEXT product reads first: (dy, j) = (0,0) (0,1) (1,0) (1,1) (2,0) (2,1) use fragments 0 1 1 2 2 3
           constexpr int call = dy * 2 + j;
           if constexpr (call == 0) relu_frag(A[gi & 1][1]);
@@ -352,7 +436,7 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
 #pragma unroll
           for (int r = 0; r < 4; ++r) ROWS_RD128(A[(gi + 1) & 1][r], ad[dx1][ks1], r * DIL * ROWB);
         }
-        if constexpr (S == 0 && gi == 0) {   // LDS operations complete in order: the read-back issued in front of A[0] is in `t` too
+        if constexpr (S == 0 && gi == 0 && !SW) {   // LDS operations complete in order: the read-back issued in front of A[0] is in `t` too
           asm volatile("s_waitcnt lgkmcnt(4)"
                        : "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[0][2]), "+v"(A[0][3]), "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1]),
                          "+v"(t[2][0]), "+v"(t[2][1]), "+v"(t[3][0]), "+v"(t[3][1])::"memory");
@@ -377,14 +461,15 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
       group(std::integral_constant<int, 4>{});
       group(std::integral_constant<int, 5>{});
       // the tile is complete: park the raw accumulators in the wave's transposition buffer; the next stage reads them back (a read
-      // issued here would be waited for in another basic block, and hipcc then copies its not-yet-loaded destination registers)
-      if constexpr (S == NSRC - 1) {
+      // issued here would be waited for in another basic block, and hipcc then copies its not-yet-loaded destination registers).
+      // SW: nothing to do -- the tile waits in its accumulator set
+      if constexpr (S == NSRC - 1 && !SW) {
         asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");   // MFMA result -> LDS-store data: wait states inline asm does not get
 #pragma unroll
         for (int j = 0; j < 2; ++j)
 #pragma unroll
           for (int r = 0; r < 16; ++r) {
-            const float v = acc[j][r];
+            const float v = acc[0][j][r];
             ROWS_WR32(a_pw, v, (j * 32 + (r & 3) + 8 * (r >> 2)) * 128);
           }
       }
@@ -394,16 +479,18 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
   // the last tile's epilogue has no next stage to hide in
   auto drain = [&](auto ktag, int k) {
     constexpr int K = decltype(ktag)::value;
+    if constexpr (!SW) {
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      ROWS_RD128(t[it][0], a_pr, it * 2048);
-      ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
+      for (int it = 0; it < 4; ++it) {
+        ROWS_RD128(t[it][0], a_pr, it * 2048);
+        ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)"
+                   : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1]), "+v"(t[2][0]), "+v"(t[2][1]), "+v"(t[3][0]), "+v"(t[3][1])::"memory");
     }
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1]), "+v"(t[2][0]), "+v"(t[2][1]), "+v"(t[3][0]), "+v"(t[3][1])::"memory");
     int pb, py0, px0;
     const bool pok = tile_of(k, pb, py0, px0);
-#define CD_M(m) epi(std::integral_constant<int, m>{}, std::integral_constant<int, K>{}, pok, pb, py0, px0);
+#define CD_M(m) epi(std::integral_constant<int, m>{}, std::integral_constant<int, K>{}, std::integral_constant<int, (SW ? K & 1 : 0)>{}, pok, pb, py0, px0);
     CD_M(0) CD_M(1) CD_M(2) CD_M(3) CD_M(4) CD_M(5) CD_M(6) CD_M(7) CD_M(8) CD_M(9) CD_M(10) CD_M(11)
     CD_M(12) CD_M(13) CD_M(14) CD_M(15) CD_M(16) CD_M(17) CD_M(18) CD_M(19) CD_M(20) CD_M(21) CD_M(22) CD_M(23)
     CD_M(24) CD_M(25) CD_M(26) CD_M(27) CD_M(28) CD_M(29) CD_M(30) CD_M(31) CD_M(32) CD_M(33) CD_M(34) CD_M(35)
@@ -429,22 +516,16 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
     if constexpr (NSRC > 1) stage(ktag, std::integral_constant<int, 1>{}, std::false_type{}, k);
     if constexpr (NSRC > 2) stage(ktag, std::integral_constant<int, 2>{}, std::false_type{}, k);
   };
-  for (int k = 0;; k += U) {
-    tile_step(std::integral_constant<int, 0>{}, k);
-    if (k + 1 >= cnt) { drain(std::integral_constant<int, 0>{}, k); break; }
-    if constexpr (U > 1) {
-      tile_step(std::integral_constant<int, 1 % U>{}, k + 1);
-      if (k + 2 >= cnt) { drain(std::integral_constant<int, 1 % U>{}, k + 1); break; }
-    }
-    if constexpr (U > 2) {
-      tile_step(std::integral_constant<int, 2 % U>{}, k + 2);
-      if (k + 3 >= cnt) { drain(std::integral_constant<int, 2 % U>{}, k + 2); break; }
-    }
-    if constexpr (U > 3) {
-      tile_step(std::integral_constant<int, 3 % U>{}, k + 3);
-      if (k + 4 >= cnt) { drain(std::integral_constant<int, 3 % U>{}, k + 3); break; }
-    }
+  static_assert(U <= 4, "the tile loop lists up to 4 tiles");
+#define CD_TILE(i)                                                                                 \
+  if constexpr (U > i) {                                                                           \
+    tile_step(std::integral_constant<int, i % U>{}, k + i);                                        \
+    if (k + i + 1 >= cnt) { drain(std::integral_constant<int, i % U>{}, k + i); break; }           \
   }
+  for (int k = 0;; k += U) {
+    CD_TILE(0) CD_TILE(1) CD_TILE(2) CD_TILE(3)
+  }
+#undef CD_TILE
   CD_VMWAIT(0);          // no LDS-DMA may land after the workgroup's LDS is released
 }
 
@@ -467,8 +548,9 @@ constexpr int NSLOT = 2;
 constexpr int ROWB = TWH * 64;
 constexpr int WB_OFF = NSLOT * SLOT;                // k-step 1 of the weights: [49 taps][64 lanes][16 B]
 constexpr int WB_BYTES = 49 * 1024;
-constexpr int PARK_OFF = WB_OFF + WB_BYTES;
-constexpr int LDS_BYTES = PARK_OFF + 4 * PARK_WAVE;
+constexpr int PARK_OFF = WB_OFF + WB_BYTES;            // the transposition buffers (park epilogue only)
+constexpr bool SW = CD_EPI_SWAP;                       // the swap epilogue, as in conv3x3_h16_dma
+constexpr int LDS_BYTES = PARK_OFF + (SW ? 0 : 4 * PARK_WAVE);
 static_assert(LDS_BYTES <= 160 * 1024, "7x7: ring + weights + transposition buffers exceed LDS");
 static_assert(4 * DPW * 64 >= NPIX * 4, "7x7: DMA instructions do not cover the halo tile");
 }  // namespace k7
@@ -477,6 +559,8 @@ template <int F>
 __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, int tilesX, int tilesY) {
   constexpr int P = k7::P, TWH = k7::TWH, NPIX = k7::NPIX, DPW = k7::DPW, SLOT = k7::SLOT, ROWB = k7::ROWB, WB_OFF = k7::WB_OFF,
                 PARK_OFF = k7::PARK_OFF;   // shadow the 3x3 kernel's file-scope constants
+  constexpr bool SW = k7::SW;
+  constexpr int NACC = SW ? 2 : 1;
   __shared__ __attribute__((aligned(16))) unsigned char smem[k7::LDS_BYTES];
   asm volatile("" ::"v"((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem) : "memory");   // only asm touches it
 
@@ -522,10 +606,11 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
     const unsigned dst = WB_OFF + (unsigned)i * 16u;
     ROWS_WR128(dst, v, 0);
   }
-  float esc[8], esh[8];
+  constexpr int NEC = SW ? 16 : 8;    // SW: the lane's 16 channels in accumulator-register order
+  float esc[NEC], esh[NEC];
 #pragma unroll
-  for (int j = 0; j < 8; ++j) {
-    const int c = 8 * (l & 3) + j;
+  for (int j = 0; j < NEC; ++j) {
+    const int c = SW ? ROWS_ACC_CHANNEL(j, hh) : 8 * (l & 3) + j;
     esc[j] = (a.scale ? a.scale[c] : 1.f) * a.alpha;
     esh[j] = (a.shift ? a.shift[c] : 0.f) * a.alpha;
   }
@@ -564,14 +649,50 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
   const unsigned a_pw = PARK_OFF + w * PARK_WAVE + (4 * hh * 32 + p) * 4;
   const unsigned a_pr = PARK_OFF + w * PARK_WAVE + (l >> 2) * 128 + (l & 3) * 32;
   const unsigned e_lane = (unsigned)l * 16u;
+  const unsigned e_lane_sw = (unsigned)(p * 64 + hh * 16);    // SW: pixel p, byte 16 hh (+ 32 for the second piece) of the pixel
+  const unsigned e_lane_ln = (unsigned)((l & 15) * 64 + ((l >> 4) & 1) * 32 + (l >> 5) * 16);   // behind line_swap(): pixel 16 s + (l & 15)
 
-  f32x16 acc[2];
+  f32x16 acc[NACC][2];    // [set][output row]: SW alternates the sets per tile (conv3x3_h16_dma)
+  if constexpr (SW) {
+#pragma unroll
+    for (int r = 0; r < 16; ++r) acc[1][0][r] = acc[1][1][r] = 0.f;
+  }
   u32x4 t[4][2];
 #pragma unroll
   for (int it = 0; it < 4; ++it) t[it][0] = t[it][1] = u32x4{0, 0, 0, 0};
   float ev[8];
-  auto epi = [&](auto mtag, bool pok, int pb, int py0, int px0) {
-    constexpr int M = decltype(mtag)::value;
+  u32x4 oq[2];
+  // the 36 micro-steps of a finished tile: epi_park / epi_swap of conv3x3_h16_dma without residual maps
+  auto epi = [&](auto mtag, auto aptag, bool pok, int pb, int py0, int px0) {
+    constexpr int M = decltype(mtag)::value, AP = decltype(aptag)::value;
+    if constexpr (SW) {
+      constexpr int row = M / 18, q = M % 18;
+      if constexpr (q < 16) {
+        float v = __builtin_fmaf(acc[AP][row][q], esc[q], esh[q]);
+        v = __builtin_fmaf(e_slope, fminf(v, 0.f), fmaxf(v, 0.f));
+        if constexpr ((q & 1) == 0) ev[0] = v;
+        else oq[q >> 3][(q & 7) >> 1] = f32_to_h2<F>(ev[0], v);
+      } else if constexpr (q == 16) {
+        oq[0] = swap_unpack(oq[0]);
+        oq[1] = swap_unpack(oq[1]);
+        if constexpr (CD_EPI_LINES) line_swap(oq[0], oq[1]);
+      } else {
+        const int y = py0 + 2 * w + row;
+        const unsigned soff = (unsigned)(((pb * H + y) * W + px0) * 64);
+        const bool ok = pok && y < H;
+        if constexpr (CD_EPI_LINES) {
+          const int x = px0 + (l & 15);
+          __builtin_amdgcn_raw_buffer_store_b128(oq[0], rs_out, (ok && x < W) ? e_lane_ln : OOB, soff, CD_ST_AUX);
+          __builtin_amdgcn_raw_buffer_store_b128(oq[1], rs_out, (ok && x + 16 < W) ? e_lane_ln : OOB, soff + 1024u, CD_ST_AUX);
+        } else {
+          const int x = px0 + p;
+          __builtin_amdgcn_raw_buffer_store_b128(oq[0], rs_out, (ok && x < W) ? e_lane_sw : OOB, soff, CD_ST_AUX);
+          __builtin_amdgcn_raw_buffer_store_b128(oq[1], rs_out, (ok && x < W) ? e_lane_sw + 32u : OOB, soff, CD_ST_AUX);
+        }
+        asm volatile("s_nop 2" : "+v"(oq[0]), "+v"(oq[1]));
+      }
+      return;
+    }
     constexpr int it = M / 9, j = M % 9;
     if constexpr (j < 8) {
       const unsigned raw = j < 4 ? t[it][0][j & 3] : t[it][1][j & 3];
@@ -593,7 +714,8 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
 #pragma unroll
   for (int i = 0; i < DPW; ++i) dma16<0>(rs_src, d_voff[i], (unsigned)((w * DPW + i) * 1024));   // tile 0 -> slot 0
   int cur = 0;
-  for (int k = 0; k < cnt; ++k) {
+  auto tile = [&](auto actag, int k) {
+    constexpr int AC = decltype(actag)::value, AP = SW ? AC ^ 1 : 0;   // accumulator sets of this tile and of the previous one
     const unsigned sb = (unsigned)cur * SLOT;
     CD_VMWAIT(0);                                        // tile k has landed (PF = 1: no younger load may be outstanding)
     asm volatile("s_barrier" ::: "memory");              // ... everybody's share too; slot cur ^ 1 is free; the LDS weights are in
@@ -603,10 +725,12 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
 #pragma unroll
       for (int ks = 0; ks < 2; ++ks) ad[dx][ks] = a_rd[dx][ks] + sb;
     u32x4 A[2][8], BL[7];
+    if constexpr (!SW) {
 #pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      ROWS_RD128(t[it][0], a_pr, it * 2048);
-      ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
+      for (int it = 0; it < 4; ++it) {
+        ROWS_RD128(t[it][0], a_pr, it * 2048);
+        ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
+      }
     }
 #pragma unroll
     for (int r = 0; r < 8; ++r) ROWS_RD128(A[0][r], ad[0][0], r * ROWB);
@@ -618,16 +742,17 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
     auto mma = [&](auto gitag, auto dytag, auto jtag) {
       constexpr int gi = decltype(gitag)::value, dy = decltype(dytag)::value, j = decltype(jtag)::value;
       constexpr int dx = gi >> 1, ks = gi & 1;
-      const u32x4 av = A[gi & 1][j + dy];
-      const u32x4 bv = ks == 0 ? bw0[dy * 7 + dx] : BL[dy];
+      const u32x4 pv = A[gi & 1][j + dy];
+      const u32x4 wv = ks == 0 ? bw0[dy * 7 + dx] : BL[dy];
+      const u32x4 av = SW ? wv : pv, bv = SW ? pv : wv;    // SW: (weights, pixels), a lane holds one pixel's 16 channels
       if constexpr (gi == 0 && dy == 0) {
         const f32x16 z = {0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f, 0.f};
-        acc[j] = paif::mfma16<F>(av, bv, z);
+        acc[AC][j] = paif::mfma16<F>(av, bv, z);
       } else {
-        acc[j] = paif::mfma16<F>(av, bv, acc[j]);
+        acc[AC][j] = paif::mfma16<F>(av, bv, acc[AC][j]);
       }
       constexpr int m = gi * 14 + dy * 2 + j;
-      if constexpr (m < 36) epi(std::integral_constant<int, m>{}, pok, pb, py0, px0);
+      if constexpr (m < 36) epi(std::integral_constant<int, m>{}, std::integral_constant<int, AP>{}, pok, pb, py0, px0);
       __builtin_amdgcn_sched_barrier(0);
     };
     auto group = [&](auto gitag) {
@@ -642,7 +767,7 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
         }
       }
       // wait for THIS group's operands: everything but what was just issued (LDS operations complete in order)
-      if constexpr (gi == 0) {
+      if constexpr (gi == 0 && !SW) {
         asm volatile("s_waitcnt lgkmcnt(15)"
                      : "+v"(A[0][0]), "+v"(A[0][1]), "+v"(A[0][2]), "+v"(A[0][3]), "+v"(A[0][4]), "+v"(A[0][5]), "+v"(A[0][6]), "+v"(A[0][7]),
                        "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1]), "+v"(t[2][0]), "+v"(t[2][1]), "+v"(t[3][0])::"memory");
@@ -669,32 +794,49 @@ __global__ __launch_bounds__(256, 1) void conv7x7_h16_dma(Args a, int ntiles, in
 #define CD_G(g) group(std::integral_constant<int, g>{});
     CD_G(0) CD_G(1) CD_G(2) CD_G(3) CD_G(4) CD_G(5) CD_G(6) CD_G(7) CD_G(8) CD_G(9) CD_G(10) CD_G(11) CD_G(12) CD_G(13)
 #undef CD_G
-    asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
+    if constexpr (!SW) {                                   // park the tile; SW: it waits in its accumulator set
+      asm volatile("s_nop 15\n\ts_nop 7" ::: "memory");
 #pragma unroll
-    for (int j = 0; j < 2; ++j)
+      for (int j = 0; j < 2; ++j)
 #pragma unroll
-      for (int r = 0; r < 16; ++r) {
-        const float v = acc[j][r];
-        ROWS_WR32(a_pw, v, (j * 32 + (r & 3) + 8 * (r >> 2)) * 128);
-      }
-    cur ^= 1;
-  }
-  // the last tile's epilogue
-  {
-#pragma unroll
-    for (int it = 0; it < 4; ++it) {
-      ROWS_RD128(t[it][0], a_pr, it * 2048);
-      ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
+        for (int r = 0; r < 16; ++r) {
+          const float v = acc[0][j][r];
+          ROWS_WR32(a_pw, v, (j * 32 + (r & 3) + 8 * (r >> 2)) * 128);
+        }
     }
-    asm volatile("s_waitcnt lgkmcnt(0)"
-                 : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1]), "+v"(t[2][0]), "+v"(t[2][1]), "+v"(t[3][0]), "+v"(t[3][1])::"memory");
+    cur ^= 1;
+  };
+  // the last tile's epilogue (it sits in accumulator set AP)
+  auto drain = [&](auto aptag) {
+    if constexpr (!SW) {
+#pragma unroll
+      for (int it = 0; it < 4; ++it) {
+        ROWS_RD128(t[it][0], a_pr, it * 2048);
+        ROWS_RD128(t[it][1], a_pr, it * 2048 + 16);
+      }
+      asm volatile("s_waitcnt lgkmcnt(0)"
+                   : "+v"(t[0][0]), "+v"(t[0][1]), "+v"(t[1][0]), "+v"(t[1][1]), "+v"(t[2][0]), "+v"(t[2][1]), "+v"(t[3][0]), "+v"(t[3][1])::"memory");
+    }
     int pb, py0, px0;
     const bool pok = tile_of(cnt - 1, pb, py0, px0);
-#define CD_M(m) epi(std::integral_constant<int, m>{}, pok, pb, py0, px0);
+#define CD_M(m) epi(std::integral_constant<int, m>{}, aptag, pok, pb, py0, px0);
     CD_M(0) CD_M(1) CD_M(2) CD_M(3) CD_M(4) CD_M(5) CD_M(6) CD_M(7) CD_M(8) CD_M(9) CD_M(10) CD_M(11)
     CD_M(12) CD_M(13) CD_M(14) CD_M(15) CD_M(16) CD_M(17) CD_M(18) CD_M(19) CD_M(20) CD_M(21) CD_M(22) CD_M(23)
     CD_M(24) CD_M(25) CD_M(26) CD_M(27) CD_M(28) CD_M(29) CD_M(30) CD_M(31) CD_M(32) CD_M(33) CD_M(34) CD_M(35)
 #undef CD_M
+  };
+  typedef std::integral_constant<int, 0> T0;
+  typedef std::integral_constant<int, 1> T1;
+  if constexpr (SW) {                                      // two accumulator sets alternate: the tile loop is unrolled by 2
+    for (int k = 0;; k += 2) {
+      tile(T0{}, k);
+      if (k + 1 >= cnt) { drain(T0{}); break; }
+      tile(T1{}, k + 1);
+      if (k + 2 >= cnt) { drain(T1{}); break; }
+    }
+  } else {
+    for (int k = 0; k < cnt; ++k) tile(T0{}, k);
+    drain(T0{});
   }
   CD_VMWAIT(0);
 }

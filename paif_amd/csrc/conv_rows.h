@@ -204,6 +204,59 @@ __device__ __forceinline__ void park_transpose(const f32x16& acc, unsigned a_pw,
   ROWS_LGKMWAIT(0, ROWS_PARKED(tq));
 }
 
+// ---- the swap step: the same transposition without LDS, for a PIXEL-PER-LANE accumulator ----
+// Both operands of a 32x32x16 MFMA have the same fragment layout (lane (l & 31, 8 (l >> 5) + j)), so which of the two maps is "lane =
+// l & 31" in the RESULT is the order of the two arguments and nothing else:
+//   mfma16<F>(pixels, weights, acc): lane (c = l & 31, hh = l >> 5), register r = 4 g + i holds pixel 8 g + 4 hh + i, channel c -- the
+//                                    layout the park step takes ([px][ch] in LDS, park_write's address);
+//   mfma16<F>(weights, pixels, acc): lane (p = l & 31, hh = l >> 5), register r = 4 g + i holds pixel p, channel 8 g + 4 hh + i -- the
+//                                    transposed result, element for element the same dot product in the same k order.
+// In the second layout a lane's 4 channels of a group g are 16 contiguous bytes of an fp32 map (byte 32 g + 16 hh of the pixel: an fp32
+// output needs no swap), and packed to 16 bits they are 2 dwords, 8 bytes at byte 16 g + 8 hh.  For a pair of groups (2 k, 2 k + 1)
+// one v_permlane32_swap per dword -- vdst = the dword of group 2 k, src = the dword of group 2 k + 1; the instruction exchanges lanes
+// 32-63 of vdst with lanes 0-31 of src -- leaves in {vdst0, vdst1, src0, src1}
+//   lanes  0-31: own group 2 k | the upper lane's group 2 k         = channels 16 k     .. 16 k + 7,  byte 32 k      of the pixel,
+//   lanes 32-63: the lower lane's group 2 k + 1 | own group 2 k + 1 = channels 16 k + 8 .. 16 k + 15, byte 32 k + 16 of the pixel:
+// one 16-byte store per pair, lane l at pixel l & 31, byte 32 k + 16 (l >> 5).  (The other operand order, or + 8 for the upper half,
+// gives a wrong image, not a fault.)  The swap is its own inverse: 16 bytes LOADED at that place (a residual map in the stored layout)
+// become {group 2 k, group 2 k + 1} of the lane's own channels by half_swap(v[0], v[2]), half_swap(v[1], v[3]).
+// The builtin, not inline asm: hipcc pads the VALU-write -> permlane-read hazard.
+__device__ __forceinline__ void half_swap(unsigned& lo, unsigned& hi) {
+  const auto r = __builtin_amdgcn_permlane32_swap(lo, hi, false, false);
+  lo = r[0];
+  hi = r[1];
+}
+// {packed group 2 k, packed group 2 k + 1} of the lane's pixel -> the 16 bytes the lane stores; and back: 16 bytes loaded in the stored
+// layout -> {group 2 k, group 2 k + 1} of the lane's own channels
+__device__ __forceinline__ u32x4 swap_unpack(u32x4 v) {
+  unsigned a = v.x, b = v.y, c = v.z, d = v.w;
+  half_swap(a, c);
+  half_swap(b, d);
+  const u32x4 o = {a, b, c, d};
+  return o;
+}
+// The two swapped pieces of a pixel row (q0: bytes 0-31 of the 32 pixels, lane l at pixel l & 31, byte 16 (l >> 5); q1: bytes 32-63)
+// -> whole 64-byte pixels per store instruction.  v_permlane16_swap exchanges the odd 16-lane rows of vdst with the even rows of src;
+// with vdst = q0 and src = q1, dword by dword, row r of the wave then holds
+//   q0: pixel l & 15,        byte 32 (r & 1) + 16 (r >> 1)        q1: pixel 16 + (l & 15), the same bytes:
+// 16 pixels x 64 B per store, the lines a store of the park epilogue writes.
+__device__ __forceinline__ void line_swap(u32x4& q0, u32x4& q1) {
+#pragma unroll
+  for (int d = 0; d < 4; ++d) {
+    unsigned a = q0[d], b = q1[d];
+    const auto r = __builtin_amdgcn_permlane16_swap(a, b, false, false);
+    q0[d] = r[0];
+    q1[d] = r[1];
+  }
+}
+// one 16-bit pair, converted as f32_to_h4<F> converts each of its two pairs
+template <int F>
+__device__ __forceinline__ unsigned f32_to_h2(float a, float b) {
+  return paif::f32_to_h4<F>(make_float4(a, b, 0.f, 0.f)).x;
+}
+// the lane's 16 epilogue constants in accumulator-register order: channel 8 (r >> 2) + 4 hh + (r & 3)
+#define ROWS_ACC_CHANNEL(r, hh) (8 * ((r) >> 2) + 4 * (hh) + ((r) & 3))
+
 // ---- host side ----
 // `total` units in runs of at least min_run on at most max_waves waves: wave g owns [g * run, (g + 1) * run)
 struct Partition {
