@@ -857,6 +857,50 @@ int paif_u2fusion_conv_bwd(const float* pack, int layer, const float* taped, con
 int paif_u2fusion_stem_bwd(const float* pack, const float* cat, const float* d_cat, float* d_x_over, float* d_x_under, int B, int H, int W,
                            paif_stream_t stream);
 
+/* SeAFusion baseline (fusion_model/SeaFusion.py of the reference; csrc/seafusion.hip, csrc/conv_slab.h).  fp32 throughout, NHWC maps.
+ * Streams: 0 vis, 1 inf.  Blocks: 2 * stream + r is RGBD r (0: 16 -> 32, C = 16; 1: 32 -> 48, C = 32) of a stream.  The slab of a block,
+ * [B,H,W,4C] (slab1: 64 channels, slab2: 128), holds its input in [0, C), dense.conv1's map in [C, 2C), dense.conv2's in [2C, 3C) and
+ * |convx| + |convy| in [3C, 4C); block r = 0 writes [0, 32) of its stream's slab2, block r = 1 writes [48 * stream, 48 * stream + 48) of
+ * enc [B,H,W,96].  dec4 / dec3 / dec2 [B,H,W,64 / 32 / 16] are the maps of decode4 .. decode2.  sgn [B,H,W,C] bytes tapes the signs of a
+ * block's two depthwise responses.  Gradient buffers use the layouts of their maps.  Matrix-core layers: 2 * block + {0 conv1, 1 conv2},
+ * 8 decode4, 9 decode3, 10 decode2.  pack: paif_seafusion_pack_floats() floats, ZEROED, then written by thirty paif_seafusion_pack_conv
+ * calls.  No host synchronisation, no allocation: capturable.  Bit-reproducible (no atomics). */
+size_t paif_seafusion_pack_floats(void);
+/* One Conv2d into the kernels' layout.  conv = 13 * stream + j with j = 0 the stream's first conv and j = 1 + 6 r + {0 dense.conv1,
+ * 1 dense.conv2, 2 convdown, 3 sobelconv.convx, 4 sobelconv.convy, 5 convup} of RGBD r; 26..29 = decode4..decode1.  b is null for the
+ * depthwise convs (they have no bias) and for no other. */
+int paif_seafusion_pack_conv(const float* w, const float* b, int conv, float* pack, paif_stream_t stream);
+/* fusion_model/SeaFusion.py:110, :115: channels [0, 16) of slab1 = LeakyReLU(0.2)(conv 3x3, pad 1, 1 -> 16) of plane b at x + b * sb. */
+int paif_seafusion_stem_fwd(const float* x, size_t sb, const float* pack, int stream_id, float* slab1, int B, int H, int W,
+                            paif_stream_t stream);
+/* LeakyReLU(0.2)(conv 3x3, pad 1), an implicit GEMM on v_mfma_f32_16x16x4_f32.  Layers 0..7: in = out = the block's slab; conv1 reads
+ * [0, C), writes [C, 2C); conv2 reads [0, 2C), writes [2C, 3C).  8: enc -> dec4, 9: dec4 -> dec3, 10: dec3 -> dec2. */
+int paif_seafusion_conv_fwd(const float* pack, int layer, const float* in, float* out, int B, int H, int W, paif_stream_t stream);
+/* fusion_model/SeaFusion.py:47-51: [3C, 4C) of slab = |convx(x)| + |convy(x)| of x = [0, C), depthwise 3x3, pad 1; WRITES sgn. */
+int paif_seafusion_sobel_fwd(const float* pack, int block, float* slab, void* sgn, int B, int H, int W, paif_stream_t stream);
+/* fusion_model/SeaFusion.py:80-84: LeakyReLU(0.1)(convdown([0, 3C)) + convup([3C, 4C))) as one 1x1 conv over the slab; out = slab2 of
+ * the stream (r = 0) or enc (r = 1). */
+int paif_seafusion_tail_fwd(const float* pack, int block, const float* slab, float* out, int B, int H, int W, paif_stream_t stream);
+/* fusion_model/SeaFusion.py:124: fused = tanh(conv 3x3, pad 1, 16 -> 1 of dec2) / 2 + 0.5. */
+int paif_seafusion_head_fwd(const float* pack, const float* dec2, float* fused, int B, int H, int W, paif_stream_t stream);
+/* Reverse of decode1: dy = d_fused * 0.5 * (1 - (2 fused - 1)^2) through the transposed conv; WRITES d_dec2. */
+int paif_seafusion_head_bwd(const float* pack, const float* fused, const float* d_fused, float* d_dec2, int B, int H, int W,
+                            paif_stream_t stream);
+/* Reverse of a matrix-core layer (input gradients): through the LeakyReLU (branch from the taped output) and the transposed conv.
+ * 10: taped dec2, d_dec2 -> d_dec3 (written); 9: dec3, d_dec3 -> d_dec4 (written); 8: dec4, d_dec4 -> d_enc (written); 0..7: taped = the
+ * slab, d_out = d_in = d_slab: the layer's own slice is read and ADDED into the channels below it (conv2 before conv1). */
+int paif_seafusion_conv_bwd(const float* pack, int layer, const float* taped, const float* d_out, float* d_in, int B, int H, int W,
+                            paif_stream_t stream);
+/* Reverse of the block's 1x1: the block's slice of d_out (d_slab2 of the stream / d_enc) through the LeakyReLU(0.1) (branch from
+ * taped_out, the map the forward wrote) and the transposed 1x1; WRITES all 4C channels of d_slab.  First of a block's four. */
+int paif_seafusion_tail_bwd(const float* pack, int block, const float* taped_out, const float* d_out, float* d_slab, int B, int H, int W,
+                            paif_stream_t stream);
+/* Reverse of the depthwise pair: [3C, 4C) of d_slab times the taped signs through the two transposed depthwise convs, ADDED into [0, C). */
+int paif_seafusion_sobel_bwd(const float* pack, int block, const void* sgn, float* d_slab, int B, int H, int W, paif_stream_t stream);
+/* Reverse of a stream's first conv: channels [0, 16) of d_slab1 through the LeakyReLU and the transposed conv -> d_x [B,H,W] (written). */
+int paif_seafusion_stem_bwd(const float* pack, int stream_id, const float* slab1, const float* d_slab1, float* d_x, int B, int H, int W,
+                            paif_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

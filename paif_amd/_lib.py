@@ -225,6 +225,18 @@ SIGNATURES = {
     "paif_u2fusion_head_bwd": (c_int, [F, F, F, F, c_int, c_int, c_int, F]),
     "paif_u2fusion_conv_bwd": (c_int, [F, c_int, F, F, F, c_int, c_int, c_int, F]),
     "paif_u2fusion_stem_bwd": (c_int, [F, F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_pack_floats": (c_size_t, []),
+    "paif_seafusion_pack_conv": (c_int, [F, F, c_int, F, F]),
+    "paif_seafusion_stem_fwd": (c_int, [F, c_size_t, F, c_int, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_conv_fwd": (c_int, [F, c_int, F, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_sobel_fwd": (c_int, [F, c_int, F, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_tail_fwd": (c_int, [F, c_int, F, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_head_fwd": (c_int, [F, F, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_head_bwd": (c_int, [F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_conv_bwd": (c_int, [F, c_int, F, F, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_tail_bwd": (c_int, [F, c_int, F, F, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_sobel_bwd": (c_int, [F, c_int, F, F, c_int, c_int, c_int, F]),
+    "paif_seafusion_stem_bwd": (c_int, [F, c_int, F, F, F, c_int, c_int, c_int, F]),
 }
 
 _lib = None

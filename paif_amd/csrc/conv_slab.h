@@ -1,0 +1,174 @@
+// The SLAB CONV: an exact-fp32 implicit GEMM on v_mfma_f32_16x16x4_f32 over a slice of an NHWC concat slab -- the conv_k of u2fusion.hip,
+// generalised by template / argument (u2fusion.hip keeps its own copy for now):
+//   * TAPS: 9 (3 x 3, zero pad 1) or 1 (1 x 1: no halo is staged);
+//   * MB in {1, 2, 3, 4} blocks of 16 output channels per workgroup (plan_for(): a 16-channel output spends no instruction on zeros);
+//   * the LeakyReLU slope is an argument: of the store epilogue (EPI_ACT) or of the input mask (MASK);
+//   * EPI_ACT adds up to two biases (a 1 x 1 over two weight matrices side by side sums both convs' biases).
+// Everything else is conv_k's.  Output CHANNELS on M, 16 PIXELS of one image row on N; the D operand of lane l is channels
+// 4 (l >> 4) .. + 3 of pixel l & 15, one float4 of the NHWC map, and the B operand of four consecutive instructions is one float4 of the
+// input map.  A workgroup of four waves owns a 16 x 16 pixel tile (four rows per wave) and MB blocks of 16 output channels (blockIdx.y
+// selects the group of MB blocks).  Per CHUNK of 16 input channels it stages the tile (+ halo 1 for 9 taps; what lies outside the image
+// is zero) as four quad planes and the chunk's weights in operand order (TAPS x MB x 1 KB), then per tap reads four pixel float4 and MB
+// weight float4 for 16 MB instructions, k ascending: a fixed summation order.  Every output quad is owned by one lane: no atomics.
+// A launch must not read channels it writes (EPI_ADD reads and writes its OWN quad only).
+// Channel counts: K and M are padded with zeros to multiples of 16 in the staged tile, the pack and the stores (out_n a multiple of 4).
+#pragma once
+#include "paif_common.h"
+
+namespace paif_slab {
+
+typedef float f32x4 __attribute__((ext_vector_type(4)));
+
+constexpr int DT = 16;   // tile edge: 4 waves x 4 rows of 16 pixels
+
+enum { EPI_ACT = 0, EPI_STORE = 1, EPI_ADD = 2 };
+
+// One operand pack: M output channels in `groups` groups of MB blocks of 16, K input channels in `chunks` chunks of 16, `taps` taps.
+struct Plan {
+  int M, K, MB, groups, chunks, taps;
+  __host__ __device__ constexpr size_t floats() const { return (size_t)groups * chunks * taps * MB * 256; }
+};
+// MB: all blocks in one group up to 4; beyond, the fewest padded blocks among 4 and 3 (a tie takes 4).
+__host__ __device__ constexpr Plan plan_for(int M, int K, int taps) {
+  const int blocks = (M + 15) / 16;
+  const int MB = blocks <= 4 ? blocks : ((blocks + 3) / 4) * 4 <= ((blocks + 2) / 3) * 3 ? 4 : 3;
+  return Plan{M, K, MB, (blocks + MB - 1) / MB, (K + 15) / 16, taps};
+}
+
+// Operand order: [group][chunk][tap][block mb][lane][j]; A[m = lane & 15][k = lane >> 4] of instruction j is the weight of output channel
+// m = 16 (group * MB + mb) + (lane & 15) and input channel k = 16 chunk + 4 (lane >> 4) + j.  `w` is a conv weight [co][n][taps] whose n
+// input channels sit at [off, off + n) of the conv's concat (several weights side by side fill one pack).  Forward (M = co, K = concat):
+// W[m][k - off][tap]; transposed (M = concat, K = co): W[k][m - off][taps - 1 - tap].  Elements outside [off, off + n) are left alone
+// (the pack starts as zeros).
+static __global__ void pack_ops_k(const float* __restrict__ w, int co, int n, int off, Plan pl, int transposed, float* __restrict__ dst) {
+  const size_t i = (size_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= pl.floats()) return;
+  const int j = i & 3, lane = (i >> 2) & 63;
+  size_t r = i >> 8;
+  const int mb = r % pl.MB;
+  r /= pl.MB;
+  const int tap = r % pl.taps;
+  r /= pl.taps;
+  const int c = r % pl.chunks, g = r / pl.chunks;
+  const int m = 16 * (g * pl.MB + mb) + (lane & 15), k = 16 * c + 4 * (lane >> 4) + j;
+  if (transposed) {
+    if (m >= off && m < off + n && k < co) dst[i] = w[((size_t)k * n + (m - off)) * pl.taps + pl.taps - 1 - tap];
+  } else {
+    if (k >= off && k < off + n && m < co) dst[i] = w[((size_t)m * n + (k - off)) * pl.taps + tap];
+  }
+}
+
+__device__ __forceinline__ float leaky(float v, float s) { return v > 0.f ? v : s * v; }
+// the branch is read off the taped OUTPUT (same sign as the pre-activation; exactly 0 takes the slope, as torch)
+__device__ __forceinline__ float dleaky(float out, float g, float s) { return out > 0.f ? g : s * g; }
+__device__ __forceinline__ float4 dleaky4(float4 f, float4 v, float s) {
+  return make_float4(dleaky(f.x, v.x, s), dleaky(f.y, v.y, s), dleaky(f.z, v.z, s), dleaky(f.w, v.w, s));
+}
+
+struct ConvArgs {
+  const float* in;      // first channel of the input slice; pixel stride in_cs floats, nq channel quads
+  const float* mask;    // MASK: the taped map of the same slice (same stride)
+  float* out;           // first channel of the output map; pixel stride out_cs; channels [out_off, out_off + out_n) are written
+  const float* wpk;     // operand pack of this conv
+  const float* bias;    // EPI_ACT
+  const float* bias2;   // EPI_ACT: a second bias, or null
+  float slope;          // LeakyReLU slope: of the stored map (EPI_ACT), of the taped map behind the input (MASK)
+  int in_cs, nq, out_cs, out_off, out_n, chunks, H, W, tx, ty;
+};
+
+template <int TAPS, int MB, bool MASK, int EPI>
+__global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
+  static_assert(TAPS == 9 || TAPS == 1, "3 x 3 or 1 x 1");
+  constexpr int HALO = TAPS == 9 ? 1 : 0, DP = DT + 2 * HALO;
+  constexpr int QS = (DP * DP + 15) / 16 * 16;   // quad stride in float4, a multiple of 256 B: quad planes start at the same LDS bank
+  __shared__ float4 s_x[4 * QS];
+  __shared__ float4 s_w[TAPS * MB * 64];
+  const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, p = lane & 15;
+  const int H = a.H, W = a.W;
+  const int b = blockIdx.x / (a.tx * a.ty), rem = blockIdx.x - b * a.tx * a.ty, by = rem / a.tx, bx = rem - by * a.tx;
+  const int y0 = by * DT, x0 = bx * DT, r0 = 4 * wave;
+  const size_t img = (size_t)b * H * W;
+  const float4* __restrict__ wg = reinterpret_cast<const float4*>(a.wpk) + (size_t)blockIdx.y * a.chunks * (TAPS * MB * 64);
+
+  f32x4 acc[MB][4];
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb)
+#pragma unroll
+    for (int r = 0; r < 4; ++r) acc[mb][r] = f32x4{0.f, 0.f, 0.f, 0.f};
+
+  for (int c = 0; c < a.chunks; ++c) {
+    if (c) __syncthreads();   // the previous chunk has been read
+    for (int e = tid; e < DP * DP * 4; e += 256) {
+      const int sq = e & 3, pix = e >> 2, ly = pix / DP, lx = pix - ly * DP, gy = y0 - HALO + ly, gx = x0 - HALO + lx, gq = 4 * c + sq;
+      float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
+      if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W && gq < a.nq) {
+        const size_t o = (img + (size_t)gy * W + gx) * a.in_cs + 4 * gq;
+        v = *reinterpret_cast<const float4*>(a.in + o);
+        if constexpr (MASK) v = dleaky4(*reinterpret_cast<const float4*>(a.mask + o), v, a.slope);
+      }
+      s_x[sq * QS + pix] = v;
+    }
+    const float4* __restrict__ wc = wg + (size_t)c * (TAPS * MB * 64);
+    for (int e = tid; e < TAPS * MB * 64; e += 256) s_w[e] = wc[e];
+    __syncthreads();
+#pragma unroll
+    for (int tap = 0; tap < TAPS; ++tap) {
+      float4 xv[4];
+#pragma unroll
+      for (int r = 0; r < 4; ++r) xv[r] = s_x[q * QS + (r0 + r + (HALO ? tap / 3 : 0)) * DP + p + (HALO ? tap % 3 : 0)];
+#pragma unroll
+      for (int mb = 0; mb < MB; ++mb) {
+        const float4 wv = s_w[(tap * MB + mb) * 64 + lane];
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[mb][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.x, xv[r].x, acc[mb][r], 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[mb][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.y, xv[r].y, acc[mb][r], 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[mb][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.z, xv[r].z, acc[mb][r], 0, 0, 0);
+#pragma unroll
+        for (int r = 0; r < 4; ++r) acc[mb][r] = __builtin_amdgcn_mfma_f32_16x16x4f32(wv.w, xv[r].w, acc[mb][r], 0, 0, 0);
+      }
+    }
+  }
+
+  const int gx = x0 + p;
+  if (gx >= W) return;
+#pragma unroll
+  for (int mb = 0; mb < MB; ++mb) {
+    const int co = 16 * ((int)blockIdx.y * MB + mb) + 4 * q;   // out_n is a multiple of 4: a quad is written whole or not at all
+    if (co >= a.out_n) continue;
+    float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);
+    if constexpr (EPI == EPI_ACT) {
+      bs = *reinterpret_cast<const float4*>(a.bias + co);
+      if (a.bias2) {
+        const float4 b2 = *reinterpret_cast<const float4*>(a.bias2 + co);
+        bs = make_float4(bs.x + b2.x, bs.y + b2.y, bs.z + b2.z, bs.w + b2.w);
+      }
+    }
+#pragma unroll
+    for (int r = 0; r < 4; ++r) {
+      const int gy = y0 + r0 + r;
+      if (gy >= H) continue;
+      float4* o = reinterpret_cast<float4*>(a.out + (img + (size_t)gy * W + gx) * a.out_cs + a.out_off + co);   // owned by this lane
+      const f32x4 v = acc[mb][r];
+      if constexpr (EPI == EPI_ACT) {
+        *o = make_float4(leaky(v[0] + bs.x, a.slope), leaky(v[1] + bs.y, a.slope), leaky(v[2] + bs.z, a.slope), leaky(v[3] + bs.w, a.slope));
+      } else if constexpr (EPI == EPI_STORE) {
+        *o = make_float4(v[0], v[1], v[2], v[3]);
+      } else {
+        const float4 u = *o;
+        *o = make_float4(u.x + v[0], u.y + v[1], u.z + v[2], u.w + v[3]);
+      }
+    }
+  }
+}
+
+template <int TAPS, bool MASK, int EPI>
+void launch_conv(int MB, dim3 grid, hipStream_t s, const ConvArgs& a) {
+  if (MB == 4) hipLaunchKernelGGL((conv_k<TAPS, 4, MASK, EPI>), grid, dim3(256), 0, s, a);
+  else if (MB == 3) hipLaunchKernelGGL((conv_k<TAPS, 3, MASK, EPI>), grid, dim3(256), 0, s, a);
+  else if (MB == 2) hipLaunchKernelGGL((conv_k<TAPS, 2, MASK, EPI>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((conv_k<TAPS, 1, MASK, EPI>), grid, dim3(256), 0, s, a);
+}
+
+}  // namespace paif_slab

@@ -2322,3 +2322,82 @@ def u2fusion_backward(cat, s1, s2, s3, fused, d_fused, pack):
         _lib.check(L.paif_u2fusion_conv_bwd(_p(pack), layer, _p(taped), _p(d_out), _p(d_in), B, H, W, _stream()), "u2fusion_conv_bwd")
     _lib.check(L.paif_u2fusion_stem_bwd(_p(pack), _p(cat), _p(d_cat), _p(d1), _p(d2), B, H, W, _stream()), "u2fusion_stem_bwd")
     return d1, d2
+
+
+# ---------------------------------------------------------------------------------------------
+# SeAFusion baseline (csrc/seafusion.hip, csrc/conv_slab.h; fusion_model/seafusion.py is the module)
+# ---------------------------------------------------------------------------------------------
+def _pb(t):
+    """Device pointer of a dense uint8 CUDA tensor (the sign tapes)."""
+    if not t.is_cuda or t.dtype != torch.uint8 or not t.is_contiguous():
+        raise RuntimeError("expected a dense uint8 CUDA tensor")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def seafusion_pack(convs):
+    """convs: the thirty (weight, bias or None) in paif_amd.synthetic.SEAFUSION_CONVS order -> the kernels' weight layout (the 3x3 and
+    1x1 convs in MFMA operand order, forward and transposed; the two 1x1 of an RGBD side by side in one pack)."""
+    dev = convs[0][0].device
+    pack = torch.zeros(lib().paif_seafusion_pack_floats(), device=dev, dtype=torch.float32)
+    for conv, (w, b) in enumerate(convs):
+        _lib.check(lib().paif_seafusion_pack_conv(_p(w.detach().contiguous()), None if b is None else _p(b.detach().contiguous()), conv,
+                                                  _p(pack), _stream()), "seafusion_pack_conv")
+    return pack
+
+
+def seafusion_forward(x_vis, x_inf, pack):
+    """Two [B,1,H,W] planes (the reference's image_vis[:, :1] and image_ir) -> (maps, fused [B,1,H,W]).  maps: slab1 [B,H,W,64] and slab2
+    [B,H,W,128] per stream (vis first), enc [B,H,W,96], dec4 / dec3 / dec2 [B,H,W,64 / 32 / 16], all fp32 NHWC, and sgn: the four sign
+    tapes [B,H,W,C] uint8 of the depthwise pairs.  22 launches."""
+    B, _, H, W = x_vis.shape
+    L = lib()
+    dev = x_vis.device
+    planes = [_plane(x_vis), _plane(x_inf)]
+
+    def new(c, dtype=torch.float32):
+        return torch.empty((B, H, W, c), device=dev, dtype=dtype)
+
+    slab1, slab2 = [new(64), new(64)], [new(128), new(128)]
+    enc, dec4, dec3, dec2 = new(96), new(64), new(32), new(16)
+    sgn = [new(16 << (k & 1), torch.uint8) for k in range(4)]
+    fused = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    for s in range(2):
+        _, p, sb = planes[s]
+        _lib.check(L.paif_seafusion_stem_fwd(p, sb, _p(pack), s, _p(slab1[s]), B, H, W, _stream()), "seafusion_stem_fwd")
+        for r, slab, out in ((0, slab1[s], slab2[s]), (1, slab2[s], enc)):
+            k = 2 * s + r
+            for layer in (2 * k, 2 * k + 1):
+                _lib.check(L.paif_seafusion_conv_fwd(_p(pack), layer, _p(slab), _p(slab), B, H, W, _stream()), "seafusion_conv_fwd")
+            _lib.check(L.paif_seafusion_sobel_fwd(_p(pack), k, _p(slab), _pb(sgn[k]), B, H, W, _stream()), "seafusion_sobel_fwd")
+            _lib.check(L.paif_seafusion_tail_fwd(_p(pack), k, _p(slab), _p(out), B, H, W, _stream()), "seafusion_tail_fwd")
+    for layer, src, dst in ((8, enc, dec4), (9, dec4, dec3), (10, dec3, dec2)):
+        _lib.check(L.paif_seafusion_conv_fwd(_p(pack), layer, _p(src), _p(dst), B, H, W, _stream()), "seafusion_conv_fwd")
+    _lib.check(L.paif_seafusion_head_fwd(_p(pack), _p(dec2), _p(fused), B, H, W, _stream()), "seafusion_head_fwd")
+    return dict(slab1=slab1, slab2=slab2, enc=enc, dec4=dec4, dec3=dec3, dec2=dec2, sgn=sgn), fused
+
+
+def seafusion_backward(maps, fused, d_fused, pack):
+    """Reverse of seafusion_forward (input gradients) from the taped maps and fused plane -> (d_x_vis, d_x_inf) [B,1,H,W].  22 launches;
+    nothing is recomputed and nothing needs a memset."""
+    B, _, H, W = fused.shape
+    L = lib()
+    d_fused = d_fused.contiguous()
+    enc, dec4, dec3, dec2 = maps["enc"], maps["dec4"], maps["dec3"], maps["dec2"]
+    d_enc, d_dec4, d_dec3, d_dec2 = (torch.empty_like(m) for m in (enc, dec4, dec3, dec2))
+    _lib.check(L.paif_seafusion_head_bwd(_p(pack), _p(fused), _p(d_fused), _p(d_dec2), B, H, W, _stream()), "seafusion_head_bwd")
+    for layer, taped, d_out, d_in in ((10, dec2, d_dec2, d_dec3), (9, dec3, d_dec3, d_dec4), (8, dec4, d_dec4, d_enc)):
+        _lib.check(L.paif_seafusion_conv_bwd(_p(pack), layer, _p(taped), _p(d_out), _p(d_in), B, H, W, _stream()), "seafusion_conv_bwd")
+    grads = []
+    for s in range(2):
+        slab1, slab2 = maps["slab1"][s], maps["slab2"][s]
+        d_slab1, d_slab2 = torch.empty_like(slab1), torch.empty_like(slab2)
+        for r, slab, d_slab, out, d_out in ((1, slab2, d_slab2, enc, d_enc), (0, slab1, d_slab1, slab2, d_slab2)):
+            k = 2 * s + r
+            _lib.check(L.paif_seafusion_tail_bwd(_p(pack), k, _p(out), _p(d_out), _p(d_slab), B, H, W, _stream()), "seafusion_tail_bwd")
+            _lib.check(L.paif_seafusion_sobel_bwd(_p(pack), k, _pb(maps["sgn"][k]), _p(d_slab), B, H, W, _stream()), "seafusion_sobel_bwd")
+            for layer in (2 * k + 1, 2 * k):
+                _lib.check(L.paif_seafusion_conv_bwd(_p(pack), layer, _p(slab), _p(d_slab), _p(d_slab), B, H, W, _stream()), "seafusion_conv_bwd")
+        d_x = torch.empty_like(fused)
+        _lib.check(L.paif_seafusion_stem_bwd(_p(pack), s, _p(slab1), _p(d_slab1), _p(d_x), B, H, W, _stream()), "seafusion_stem_bwd")
+        grads.append(d_x)
+    return grads[0], grads[1]

@@ -157,6 +157,41 @@ def u2fusion_state_dict(scales, shift):
     return sd
 
 
+# The thirty convs of the SeAFusion baseline (reference fusion_model/SeaFusion.py:86-104) in module order, as (state_dict prefix, out
+# channels, in channels per group, kernel size, has a bias): the order of ops.seafusion_pack.  The depthwise pair of an RGBD has one
+# input channel per group and no bias.
+def _rgbd_convs(prefix, c, cout):
+    return ((prefix + ".dense.conv1.conv", c, c, 3, True), (prefix + ".dense.conv2.conv", c, 2 * c, 3, True),
+            (prefix + ".convdown.conv", cout, 3 * c, 1, True), (prefix + ".sobelconv.convx", c, 1, 3, False),
+            (prefix + ".sobelconv.convy", c, 1, 3, False), (prefix + ".convup.conv", cout, c, 1, True))
+
+
+SEAFUSION_CONVS = (sum((((s + "_conv.conv", 16, 1, 3, True),) + _rgbd_convs(s + "_rgbd1", 16, 32) + _rgbd_convs(s + "_rgbd2", 32, 48)
+                        for s in ("vis", "inf")), ())
+                   + (("decode4.conv", 64, 96, 3, True), ("decode3.conv", 32, 64, 3, True), ("decode2.conv", 16, 32, 3, True),
+                      ("decode1.conv", 1, 16, 3, True)))
+SEAFUSION_BN = (("decode4.bn", 64), ("decode3.bn", 32), ("decode2.bn", 16), ("decode1.bn", 1))   # owned, never applied
+
+
+def seafusion_state_dict(scales, shift):
+    """key -> numpy array (72 entries): formula_tensor("sea/" + key) times the conv's scale (weight and bias alike, the eight depthwise
+    convs included: they are NOT the Sobel stencil), `shift` added to decode1.conv.bias, and formula values for the decoder's unused
+    BatchNorm entries.  tools/make_golden_seafusion.py and the tests rebuild the fixture weights with this one expression."""
+    scales = np.asarray(scales, dtype=np.float32)
+    assert scales.shape == (len(SEAFUSION_CONVS),)
+    sd = {}
+    for (name, cout, cin, k, bias), s in zip(SEAFUSION_CONVS, scales):
+        sd[name + ".weight"] = formula_tensor("sea/" + name + ".weight", (cout, cin, k, k)) * s
+        if bias:
+            sd[name + ".bias"] = formula_tensor("sea/" + name + ".bias", (cout,)) * s
+    sd["decode1.conv.bias"] = sd["decode1.conv.bias"] + np.float32(shift)
+    for name, c in SEAFUSION_BN:
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            sd["%s.%s" % (name, leaf)] = formula_tensor("sea/%s.%s" % (name, leaf), (c,))
+        sd[name + ".num_batches_tracked"] = formula_tensor("sea/" + name + ".num_batches_tracked", ())
+    return sd
+
+
 # --------------------------------------------------------------------------------------
 # inputs
 # --------------------------------------------------------------------------------------

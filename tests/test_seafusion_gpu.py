@@ -1,0 +1,531 @@
+"""GPU: the SeAFusion baseline (paif_amd/fusion_model/seafusion.py, csrc/seafusion.hip, csrc/conv_slab.h) against the reference's own
+outputs and autograd (tests/golden/gs_seafusion*.npz, generated on the CPU by tools/make_golden_seafusion.py), and inside the composite
+model / attack / harness flow of the searched network.
+
+Bound of the kernel parity checks (tests/test_u2fusion_gpu.py): with floor = max|ref32 - ref64| of the same tensor,
+max|hip - ref64| <= 1.5 * floor + 1e-5 * max(1, max|ref64|).  One kernel form exists (exact fp32, the 3x3 and 1x1 convs on
+v_mfma_f32_16x16x4_f32); it is the default build.
+
+In the fixtures i1 is the infrared plane and enters image_vis, i2 is the visible Y plane and enters image_ir: the order inside the
+composite model.
+
+The reference's autograd is the yardstick of the input gradients only where none of the 688 sign points per pixel (LeakyReLU inputs at both
+slopes, depthwise responses under abs) is within fp32 reach of zero (the five small cases, see the tool).  At 1x37x53 and 2x24x32 the
+reverse pass is tested as what it is given its tape -- a linear map -- against a float64 restatement that takes its LeakyReLU branches and
+tanh' from the tape itself and the signs of the depthwise responses from a float64 recomputation on the taped input map."""
+import numpy as np
+import pytest
+import torch
+import torch.nn.functional as F
+
+from paif_amd import ops, synthetic as S
+from tests import helpers as Hh
+from tests.helpers import t, maxabs
+
+pytestmark = pytest.mark.gpu
+
+GRAD_CASES = ("1x4x5", "1x13x17", "2x9x20", "1x5x37", "1x19x18")
+LARGE = ("1x37x53", "2x24x32")
+SMALL = ("1x4x5", "1x13x17")
+MAP_CHANNELS = [16, 16, 16, 16, 32, 32, 32, 32, 48] * 2 + [64, 32, 16]
+EPS, ALPHA = 8 / 255., 2 / 255.
+_SD = {}
+
+
+def _dev():
+    assert torch.cuda.is_available()
+    return torch.device("cuda:0")
+
+
+def _sd(golden):
+    """The fixture weights, rebuilt once from the thirty scales and the shift."""
+    if not _SD:
+        g = golden("gs_seafusion")
+        _SD.update({k: torch.from_numpy(np.asarray(v)) for k, v in S.seafusion_state_dict(g["scales"], g["shift"]).items()})
+    return _SD
+
+
+def _net(golden):
+    from paif_amd.fusion_model.seafusion import SeaFusion
+
+    net = SeaFusion().eval()
+    net.load_state_dict(_sd(golden), strict=True)
+    return net.requires_grad_(False).to(_dev())
+
+
+def _inputs(golden, case):
+    g = golden("gs_seafusion_" + case)
+    cot = g["cot"] if "cot" in g else S.make_feature(900 + len(case), g["i1"].shape)
+    return t(g["i1"]).to(_dev()), t(g["i2"]).to(_dev()), t(cot).to(_dev())
+
+
+def _bound(floor, ref64):
+    return 1.5 * floor + 1e-5 * max(1.0, float(np.abs(ref64).max()))
+
+
+def _floor(ref32, ref64):
+    return float(np.abs(ref32.astype(np.float64) - ref64).max())
+
+
+def _border(a):
+    """The outermost 10 rows / columns (the total halo of the ten 3 x 3 convs on the longest path) of [..., H, W]."""
+    m = np.ones(a.shape[-2:], dtype=bool)
+    m[10:-10, 10:-10] = False
+    return a[..., m]
+
+
+def _check(what, case, name, mine, ref64, floor, border=False, keep=None):
+    got = mine.detach().cpu().numpy().astype(np.float64)
+    assert got.shape == ref64.shape
+    if keep is not None:                       # excluded elements take no part: neither in the error nor in the border check
+        got = np.where(keep, got, ref64)
+    bound = _bound(floor, ref64)
+    err = float(np.abs(got - ref64).max())
+    print("%s %s %s: err %.3e bound %.3e ratio %.3f scale %.3e" % (what, case, name, err, bound, err / bound, float(np.abs(ref64).max())))
+    assert err <= bound, (name, err, bound)
+    if border:
+        eb = float(np.abs(_border(got) - _border(ref64)).max())
+        print("%s %s %s border: err %.3e bound %.3e ratio %.3f" % (what, case, name, eb, bound, eb / bound))
+        assert eb <= bound, (name, "border", eb, bound)
+
+
+@pytest.mark.parametrize("case", GRAD_CASES + LARGE)
+def test_fused_plane_matches_the_reference(golden, case):
+    """1x4x5 is smaller than the total halo of 10 (all border), 1x13x17 is ragged in both directions with two tiles across, 2x9x20 has two
+    images, 1x5x37 three tiles across with the last 5 pixels wide, 1x19x18 2 x 2 tiles ragged in both, 1x37x53 and 2x24x32 several tile
+    rows and columns."""
+    g = golden("gs_seafusion_" + case)
+    net = _net(golden)
+    i1, i2, _ = _inputs(golden, case)
+    with torch.no_grad():
+        out = net(i1, i2)
+    assert out.grad_fn is None and out.shape == i1.shape
+    _check("fused", case, "fused", out, g["fused64"], _floor(g["fused"], g["fused64"]), border=case in LARGE)
+
+
+@pytest.mark.parametrize("case", SMALL)
+def test_feature_maps_match_the_reference(golden, case):
+    """The 21 taped maps (592 channels: per stream the first conv, and per RGBD conv1, conv2, |convx| + |convy| and the output; decode4 ..
+    decode2), each against its own floor."""
+    parts = [golden("gs_seafusion_%s_maps%d" % (case, p)) for p in (0, 1)]
+    net = _net(golden)
+    i1, i2, _ = _inputs(golden, case)
+    maps = net._features(i1, i2)
+    assert [m.shape[1] for m in maps] == MAP_CHANNELS and sum(MAP_CHANNELS) == 592
+    for k, m in enumerate(maps):
+        g = parts[0 if k < 9 else 1]
+        _check("maps", case, "map%d" % k, m, g["map%d" % k], float(g["map_floor"][k]))
+
+
+@pytest.mark.parametrize("case", GRAD_CASES)
+def test_input_gradients_match_float64_autograd(golden, case):
+    """d_i1, d_i2 for the fixture's cotangent on the fused plane, through forward + .backward()."""
+    g = golden("gs_seafusion_" + case)
+    net = _net(golden)
+    i1, i2, cot = _inputs(golden, case)
+    a, b = i1.clone().requires_grad_(True), i2.clone().requires_grad_(True)
+    out = net(a, b)
+    assert out.grad_fn is not None
+    (out * cot).sum().backward()
+    for name, mine in (("d_i1", a.grad), ("d_i2", b.grad)):
+        _check("grad", case, name, mine, g[name + "64"], _floor(g[name], g[name + "64"]))
+
+
+def _nchw(m):
+    return m.permute(0, 3, 1, 2).contiguous()
+
+
+def _taped_branches(sd, maps):
+    """From the tape (on the CPU): per stream and RGBD the LeakyReLU masks and the signs of the two depthwise responses, recomputed in
+    float64 from the taped input map -> (branches, keep): keep [B,1,H,W] is False where the 5 x 5 neighbourhood holds a response whose
+    float64 magnitude is below the float32 floor of that response map (its sign is not decided at fp32)."""
+    def mask(m, slope):
+        return torch.where(_nchw(m) > 0, 1.0, slope)
+
+    br, near = {}, None
+    for s, name in enumerate(("vis", "inf")):
+        s1, s2 = maps["slab1"][s].cpu(), maps["slab2"][s].cpu()
+        br[name + "_conv"] = mask(s1[..., 0:16], 0.2)
+        for r, slab, C, out in ((1, s1, 16, s2[..., 0:32]), (2, s2, 32, maps["enc"].cpu()[..., 48 * s:48 * s + 48])):
+            p = "%s_rgbd%d" % (name, r)
+            br[p + ".conv1"], br[p + ".conv2"], br[p + ".out"] = mask(slab[..., C:2 * C], 0.2), mask(slab[..., 2 * C:3 * C], 0.2), mask(out, 0.1)
+            x = _nchw(slab[..., 0:C])
+            for d in ("convx", "convy"):
+                w = sd["%s.sobelconv.%s.weight" % (p, d)]
+                r64 = F.conv2d(x.double(), w.double(), padding=1, groups=C)
+                r32 = F.conv2d(x, w, padding=1, groups=C)
+                floor = (r32.double() - r64).abs().max()
+                br["%s.%s" % (p, d)] = torch.sign(r64)
+                n = (r64.abs() < floor).double().amax(1, keepdim=True)
+                near = n if near is None else torch.maximum(near, n)
+    for k in ("dec4", "dec3", "dec2"):
+        br[k] = mask(maps[k].cpu(), 0.2)
+    keep = F.max_pool2d(near, 5, stride=1, padding=2) == 0
+    return br, keep.numpy()
+
+
+def _linearised(sd, br, dtanh, i1, i2, cot, dtype):
+    """The network with every LeakyReLU replaced by the constant mask of its taped map, abs by the constant sign, the tanh by its taped
+    derivative, biases dropped: what the reverse pass transposes.  -> (d_i1, d_i2) for the cotangent, by torch's CPU autograd in `dtype`."""
+    def w(name):
+        return sd[name + ".weight"].to(dtype)
+
+    def m(name):
+        return br[name].to(dtype)
+
+    a, b = i1.to(dtype).clone().requires_grad_(True), i2.to(dtype).clone().requires_grad_(True)
+    enc = []
+    for name, plane in (("vis", a), ("inf", b)):
+        x = F.conv2d(plane, w(name + "_conv.conv"), padding=1) * m(name + "_conv")
+        for r in (1, 2):
+            p = "%s_rgbd%d" % (name, r)
+            C = x.shape[1]
+            x1 = F.conv2d(x, w(p + ".dense.conv1.conv"), padding=1) * m(p + ".conv1")
+            x2 = F.conv2d(torch.cat((x, x1), 1), w(p + ".dense.conv2.conv"), padding=1) * m(p + ".conv2")
+            g = (F.conv2d(x, w(p + ".sobelconv.convx"), padding=1, groups=C) * m(p + ".convx")
+                 + F.conv2d(x, w(p + ".sobelconv.convy"), padding=1, groups=C) * m(p + ".convy"))
+            x = (F.conv2d(torch.cat((x, x1, x2), 1), w(p + ".convdown.conv")) + F.conv2d(g, w(p + ".convup.conv"))) * m(p + ".out")
+        enc.append(x)
+    x = torch.cat(enc, 1)
+    for k, name in (("dec4", "decode4"), ("dec3", "decode3"), ("dec2", "decode2")):
+        x = F.conv2d(x, w(name + ".conv"), padding=1) * m(k)
+    y = F.conv2d(x, w("decode1.conv"), padding=1) * dtanh.to(dtype)
+    (y * cot.to(dtype)).sum().backward()
+    return a.grad.numpy(), b.grad.numpy()
+
+
+@pytest.mark.parametrize("case", LARGE)
+def test_reverse_pass_matches_its_float64_restatement_on_the_taped_branches(golden, case):
+    """Sizes the margin condition cannot reach.  A LeakyReLU sign the GPU forward decided differently from the reference cannot enter: the
+    branches are the tape's.  The sign under abs is recomputed in float64 from the taped input map; where the fp32 response is too close
+    to zero for that (5 x 5 around it) the output pixel is left out, at most 1 % of them.  A wrong tap, slice offset or mask shows at order
+    0.1.  The floor is the same restatement in float32."""
+    net = _net(golden)
+    i1, i2, cot = _inputs(golden, case)
+    tape = {}
+    with torch.no_grad():
+        net.forward_impl(i1, i2, tape=tape)
+        d1, d2 = net.backward_impl(cot, tape)
+    br, keep = _taped_branches(_sd(golden), tape["maps"])
+    share = 1.0 - float(keep.mean())
+    print("taped-mask reverse %s: excluded share %.5f (the reference's own: %.5f)" % (case, share, float(golden("gs_seafusion")["case_" + case][4])))
+    assert share <= 0.01
+    tt = 2 * tape["out"].cpu().double() - 1
+    dtanh = 0.5 * (1 - tt * tt)
+    r64 = _linearised(_sd(golden), br, dtanh, i1.cpu(), i2.cpu(), cot.cpu(), torch.float64)
+    r32 = _linearised(_sd(golden), br, dtanh, i1.cpu(), i2.cpu(), cot.cpu(), torch.float32)
+    for name, mine, a64, a32 in (("d_i1", d1, r64[0], r32[0]), ("d_i2", d2, r64[1], r32[1])):
+        _check("taped-mask reverse", case, name, mine, a64, _floor(a32, a64), border=True, keep=keep)
+
+
+def _flat(tape):
+    m = tape["maps"]
+    return [tape["out"]] + m["slab1"] + m["slab2"] + [m["enc"], m["dec4"], m["dec3"], m["dec2"]] + m["sgn"]
+
+
+def test_reverse_pass_is_linear_in_the_cotangent(golden):
+    """backward_impl(g1) + backward_impl(g2) = backward_impl(g1 + g2) to fp32 rounding (tests/test_u2fusion_gpu.py's check and bound)."""
+    net = _net(golden)
+    i1, i2, cot = _inputs(golden, "1x19x18")
+    tape = {}
+    with torch.no_grad():
+        net.forward_impl(i1, i2, tape=tape)
+        g2 = t(S.make_feature(77, tuple(cot.shape))).to(_dev())
+        r1, r2, r12 = net.backward_impl(cot, tape), net.backward_impl(g2, tape), net.backward_impl(ops.add(cot, g2), tape)
+    for x, y, z in zip(r1, r2, r12):
+        scale = max(1.0, float(z.abs().max()))
+        err = float((x + y - z).abs().max())
+        print("linearity: err %.3e scale %.3e" % (err, scale))
+        assert err <= 1e-4 * scale
+
+
+def test_two_runs_are_bit_identical(golden):
+    net = _net(golden)
+    i1, i2, cot = _inputs(golden, "2x24x32")
+    runs = []
+    with torch.no_grad():
+        for _ in range(2):
+            tape = {}
+            f = net.forward_impl(i1, i2, tape=tape)
+            runs.append([f] + _flat(tape) + list(net.backward_impl(cot, tape)))
+    for x, y in zip(*runs):
+        assert torch.equal(x, y)
+
+
+def test_channel_slices_are_taken_without_a_copy(golden):
+    """The composite hands over ir[:, 0:1] and ycc of multi-channel tensors: planes addressed through their batch stride.  forward itself
+    takes image_vis[:, :1] of any channel count."""
+    net = _net(golden)
+    i1, i2, cot = _inputs(golden, "2x24x32")
+    wide1 = torch.cat([i1, i1 * 0.5, i1 * 0.25], 1).contiguous()
+    wide2 = torch.cat([i2, i2 * 0.5], 1).contiguous()
+    with torch.no_grad():
+        ta, tb = {}, {}
+        fa = net.forward_impl(i1, i2, tape=ta)
+        fb = net.forward_impl(wide1, wide2, tape=tb)
+        assert torch.equal(fa, fb)
+        assert torch.equal(fa, net(wide1[:, 0:1], wide2[:, 0:1]))
+        assert torch.equal(fa, net(wide1, wide2[:, 0:1]))
+        for x, y in zip(net.backward_impl(cot, ta), net.backward_impl(cot, tb)):
+            assert torch.equal(x, y)
+
+
+def test_settings_that_do_not_apply_change_nothing(golden):
+    """One arithmetic: the storage mode, the conv / GEMM precision and two_stream leave every bit where it is."""
+    net = _net(golden)
+    i1, i2, cot = _inputs(golden, "1x13x17")
+    with torch.no_grad():
+        tape = {}
+        base = (net.forward_impl(i1, i2, tape=tape),) + tuple(net.backward_impl(cot, tape))
+    old = dict(ops.CONFIG)
+    try:
+        for storage, conv, gemm, two in (("bf16", "f32", "f32", True), ("f16", "bf16x3", "bf16x3", False)):
+            ops.set_storage(storage), ops.set_conv_precision(conv), ops.set_gemm_precision(gemm)
+            ops.CONFIG["two_stream"] = two
+            with torch.no_grad():
+                tape = {}
+                got = (net.forward_impl(i1, i2, tape=tape),) + tuple(net.backward_impl(cot, tape))
+            assert all(x.dtype == torch.float32 for x in _flat(tape)[:-4])
+            for x, y in zip(base, got):
+                assert torch.equal(x, y)
+    finally:
+        ops.set_storage(old["storage"]), ops.set_conv_precision(old["conv_precision"]), ops.set_gemm_precision(old["gemm_precision"])
+        ops.CONFIG["two_stream"] = old["two_stream"]
+
+
+def test_wrong_planes_are_refused_on_the_device(golden):
+    net = _net(golden)
+    z = torch.zeros(1, 1, 8, 8, device=_dev())
+    with pytest.raises(TypeError, match="fp32"):
+        net(z.half(), z.half())
+    with pytest.raises(ValueError, match=r"\[B,1,H,W\]"):
+        net(z, torch.zeros(1, 1, 8, 9, device=_dev()))
+    with pytest.raises(ValueError, match=r"\[B,1,H,W\]"):                      # image_ir has one channel
+        net(torch.zeros(1, 3, 8, 8, device=_dev()), torch.zeros(1, 3, 8, 8, device=_dev()))
+    trainable = _net(golden).requires_grad_(True)
+    with pytest.raises(NotImplementedError, match="[Pp]arameter gradients"):
+        trainable(z, z)
+    with ops.no_param_grads():                                  # an attack's forward: input gradients only
+        a = z.clone().requires_grad_(True)
+        out = trainable(a, z)
+        out.sum().backward()
+    assert a.grad is not None and all(p.grad is None for p in trainable.parameters())
+
+
+def test_train_mode_equals_eval_mode_bit_for_bit(golden):
+    """The decoder's BatchNorm modules are owned and never applied: their (non-trivial) fixture values and the mode change no bit, and no
+    running statistic moves."""
+    net = _net(golden)
+    i1, i2, cot = _inputs(golden, "1x13x17")
+    before = {k: v.clone() for k, v in net.state_dict().items() if ".bn." in k}
+    assert len(before) == 20 and float((before["decode4.bn.running_mean"]).abs().max()) > 0
+    with torch.no_grad():
+        tape = {}
+        base = (net.forward_impl(i1, i2, tape=tape),) + tuple(net.backward_impl(cot, tape))
+        net.train()
+        tape = {}
+        got = (net.forward_impl(i1, i2, tape=tape),) + tuple(net.backward_impl(cot, tape)) + (net(i1, i2),)
+    for x, y in zip(base + (base[0],), got):
+        assert torch.equal(x, y)
+    for k, v in net.state_dict().items():
+        if ".bn." in k:
+            assert torch.equal(v, before[k]), k
+
+
+def _eager(net, image_vis, image_ir):
+    """fusion_model/SeaFusion.py:105-125 restated with torch's own convs on the module's parameters."""
+    def cl(mod, x):
+        return F.leaky_relu(F.conv2d(x, mod.conv.weight, mod.conv.bias, padding=1), 0.2)
+
+    def rgbd(blk, x):
+        C = x.shape[1]
+        x1 = torch.cat((x, cl(blk.dense.conv1, x)), 1)
+        x1 = torch.cat((x1, cl(blk.dense.conv2, x1)), 1)
+        x1 = F.conv2d(x1, blk.convdown.conv.weight, blk.convdown.conv.bias)
+        g = (F.conv2d(x, blk.sobelconv.convx.weight, None, padding=1, groups=C).abs()
+             + F.conv2d(x, blk.sobelconv.convy.weight, None, padding=1, groups=C).abs())
+        return F.leaky_relu(x1 + F.conv2d(g, blk.convup.conv.weight, blk.convup.conv.bias), 0.1)
+
+    v = rgbd(net.vis_rgbd2, rgbd(net.vis_rgbd1, cl(net.vis_conv, image_vis[:, :1])))
+    i = rgbd(net.inf_rgbd2, rgbd(net.inf_rgbd1, cl(net.inf_conv, image_ir)))
+    x = cl(net.decode2, cl(net.decode3, cl(net.decode4, torch.cat((v, i), 1))))
+    return torch.tanh(F.conv2d(x, net.decode1.conv.weight, net.decode1.conv.bias, padding=1)) / 2 + 0.5
+
+
+def test_reference_initialisation_matches_torch_eager(golden):
+    """A net as the constructor leaves it: torch's default conv initialisation and the Sobel stencils in convx / convy, the values a user's
+    checkpoint is most likely to hold there (exact zeros among the taps, exact-zero responses on flat patches)."""
+    from paif_amd.fusion_model.seafusion import SeaFusion
+
+    torch.manual_seed(20)
+    net = SeaFusion().eval().requires_grad_(False).to(_dev())
+    sob = torch.tensor([[1., 0., -1.], [2., 0., -2.], [1., 0., -1.]], device=_dev())
+    assert torch.equal(net.vis_rgbd2.sobelconv.convx.weight, sob.expand(32, 1, 3, 3))
+    assert torch.equal(net.inf_rgbd1.sobelconv.convy.weight, sob.t().expand(16, 1, 3, 3))
+    i1, i2, _ = _inputs(golden, "1x13x17")
+    with torch.no_grad():
+        mine, ref = net(i1, i2), _eager(net, i1, i2)
+    err = float((mine - ref).abs().max())
+    print("reference initialisation: err %.3e (fused in [%.3f, %.3f])" % (err, float(ref.min()), float(ref.max())))
+    assert float(ref.max() - ref.min()) > 1e-3
+    assert err <= 1e-5
+
+
+# ---- inside the composite model ------------------------------------------------------------------------------------------------
+@pytest.fixture
+def exact_arithmetic():
+    """The setting tests/test_attack_gpu.py asserts gradient parity under: exact-fp32 conv and GEMM kernels."""
+    old, oldg = ops.CONFIG["conv_precision"], ops.CONFIG["gemm_precision"]
+    ops.set_conv_precision("f32")
+    ops.set_gemm_precision("f32")
+    yield
+    ops.set_conv_precision(old)
+    ops.set_gemm_precision(oldg)
+
+
+def _composite(golden):
+    """As tests/test_u2fusion_gpu.py:_composite, with SeaFusion as the fusion module; its weights are the fixture's."""
+    from paif_amd.core.model_fusion_auto import Network_MM_CompModel
+    from paif_amd.fusion_model.seafusion import SeaFusion
+
+    m = Network_MM_CompModel(SeaFusion(), None, None, "mit_b0", num_classes=9).eval()
+    S.load_formula_weights(m, head=Hh.HEAD64["mit_b0"])
+    m.enhance_net.load_state_dict(_sd(golden), strict=True)
+    return m.to(_dev())
+
+
+def _batch(start=0):
+    ir, vis, lab = S.make_batch(2, 64, 96, start=start)
+    return t(ir).to(_dev()), t(vis).to(_dev()), t(lab).to(_dev())
+
+
+def _scale(a):
+    return max(1.0, float(np.abs(a).max()))
+
+
+def test_composite_clean_forward(golden):
+    """Tolerances of tests/test_u2fusion_gpu.py::test_composite_clean_forward: fused 1e-4, logits 2e-4 x scale, argmax agreement 99.9 %."""
+    g = golden("gs_seafusion_attack")
+    m = _composite(golden)
+    ir, vis, lab = _batch(int(g["start"]))
+    with torch.no_grad():
+        fused, seg = m(ir, vis)
+    print("composite: fused err %.3e logits err %.3e (scale %.3e)" % (maxabs(fused.cpu(), g["fused"]), maxabs(seg.cpu(), g["logits"]),
+                                                                    _scale(g["logits"])))
+    assert maxabs(fused.cpu(), g["fused"]) <= 1e-4
+    assert maxabs(seg.cpu(), g["logits"]) <= 2e-4 * _scale(g["logits"])
+    up = torch.nn.functional.interpolate(seg.cpu(), size=lab.shape[1:], mode="bilinear", align_corners=False)
+    agree = (up.argmax(1).numpy() == g["pred"]).mean()
+    print("composite: argmax agreement %.5f" % agree)
+    assert agree >= 0.999
+
+
+def _check_attack(g, d_ir, d_vis, trace, loss_rtol, frac):
+    """tests/test_attack_gpu.py:_check_attack."""
+    losses = np.array([s["loss"] for s in trace])
+    np.testing.assert_allclose(losses, g["losses"], rtol=loss_rtol)
+    for mine, ref in ((trace[-1]["g_ir"], g["gsum_ir"]), (trace[-1]["g_vis"], g["gsum_vis"])):
+        mism = (np.sign(mine.cpu().numpy()) != np.sign(ref)).mean()
+        print("attack: sign mismatch of the running sum %.2e" % mism)
+        assert mism <= frac
+    for mine, ref in ((d_ir, g["delta_ir"]), (d_vis, g["delta_vis"])):
+        a = mine.detach().cpu().numpy()
+        diff = (np.abs(a - ref) > 1e-6).mean()
+        print("attack: share of differing delta elements %.2e" % diff)
+        assert diff <= frac
+        assert np.abs(a).max() <= 8 / 255. + 1e-7
+
+
+def test_attack_both_pgd_through_the_baseline(golden, exact_arithmetic):
+    from paif_amd.attack.attack import attack_both
+
+    g = golden("gs_seafusion_attack")
+    m = _composite(golden)
+    assert hasattr(m, "forward_taped")                       # the fast path of attack.py is the one taken
+    ir, vis, lab = _batch(int(g["start"]))
+    trace = []
+    with torch.no_grad():
+        d_ir, d_vis = attack_both(m, vis, ir, lab, epsilon=EPS, alpha=ALPHA, attack_iters=3, attack_loss='l_seg', attack_way='PGD',
+                                  delta0_ir=t(g["d0_ir"]), delta0_vis=t(g["d0_vis"]), trace=trace)
+    for s in trace:
+        assert s["g_ir"].grad_fn is None and s["g_vis"].grad_fn is None and not s["g_ir"].requires_grad
+    print("attack: losses %s reference %s" % ([s["loss"] for s in trace], list(g["losses"])))
+    _check_attack(g, d_ir, d_vis, trace, 1e-4, 2e-3)
+
+
+def _pgd_iterations(m, ir, vis, lab64, d_ir, d_vis, g_ir, g_vis, gs, iters):
+    """The fast path of attack.py:_attack_loop, in place on d_*, g_* (so that it can be captured)."""
+    for i in range(iters):
+        with ops.attack_forward_arithmetic():
+            _, logits, tape = m.forward_taped(ops.add(ir, d_ir), ops.add(vis, d_vis))
+        way, wt, wf = ops.attack_loss_weights('PGD', i, iters)
+        coef = ops.attack_loss_fwd(logits, lab64, way, wt, wf)
+        d32 = ops.attack_loss_bwd(logits, lab64, coef, way, wt, wf, upstream=gs)
+        with ops.attack_backward_arithmetic():
+            gi, gv = m.backward_taped(d32, tape)
+        ops.axpy_(g_ir, gi.contiguous(), 1.0 / gs)
+        ops.pgd_step_(d_ir, g_ir, ir, ALPHA, EPS)
+        ops.axpy_(g_vis, gv.contiguous(), 1.0 / gs)
+        ops.pgd_step_(d_vis, g_vis, vis, ALPHA, EPS)
+
+
+def test_pgd_iterations_replayed_from_a_graph_are_bit_identical(golden):
+    """Three PGD iterations captured once with torch.cuda.graph and replayed = the eager loop.  Single stream, no parallel branches; every
+    weight pack is built before the capture."""
+    g = golden("gs_seafusion_attack")
+    m = _composite(golden)
+    ir, vis, lab = _batch(int(g["start"]))
+    lab64 = lab.type(torch.long).contiguous()
+    d0_ir, d0_vis = t(g["d0_ir"]).to(_dev()), t(g["d0_vis"]).to(_dev())
+    state = [torch.zeros_like(x) for x in (ir, vis, ir, vis)]
+
+    def reset():
+        state[0].copy_(d0_ir), state[1].copy_(d0_vis), state[2].zero_(), state[3].zero_()
+
+    gstream = torch.cuda.Stream()
+    graph = torch.cuda.CUDAGraph()
+    with torch.no_grad(), ops.attack_arithmetic():
+        gs = ops.attack_grad_scale(lab64)
+        reset()
+        _pgd_iterations(m, ir, vis, lab64, *state, gs, 3)     # eager: also builds every weight pack outside the capture
+        eager = [x.clone() for x in state]
+        torch.cuda.synchronize()
+        with torch.cuda.stream(gstream):
+            reset()
+            _pgd_iterations(m, ir, vis, lab64, *state, gs, 3)
+            torch.cuda.synchronize()
+            with torch.cuda.graph(graph, stream=gstream):
+                _pgd_iterations(m, ir, vis, lab64, *state, gs, 3)
+        torch.cuda.synchronize()
+        reset()
+        torch.cuda.synchronize()
+        graph.replay()
+        torch.cuda.synchronize()
+    assert float(eager[2].abs().max()) > 0
+    for x, y in zip(eager, state):
+        assert torch.equal(x, y)
+
+
+def test_robustness_harnesses_run_with_the_baseline(golden):
+    """val_segformer_robust2 (clean) and val_segformer_robust (PGD, 2 iterations) on two 2x64x96 batches: finite mIoU, and the clean one is
+    what the confusion matrix of the model's own seg_map argmax gives."""
+    from oracle import paif_oracle as O
+    from paif_amd.harness import val_segformer_robust, val_segformer_robust2
+
+    m = _composite(golden)
+    batches = []
+    for start in (0, 2):
+        ir, vis, lab = _batch(start)
+        batches.append((vis, ir, lab))
+    clean = val_segformer_robust2(m, batches)
+    conf = np.zeros((9, 9), dtype=np.int64)
+    with torch.no_grad():
+        for vis, ir, lab in batches:
+            _, seg = m(ir, vis)
+            up = torch.nn.functional.interpolate(seg.cpu(), size=lab.shape[1:], mode="bilinear", align_corners=False)
+            conf += O.confusion_matrix(lab.cpu().numpy(), up.argmax(1).numpy())
+    iou = O.compute_results(conf)[2]
+    assert np.isfinite(clean["miou"])
+    assert abs(clean["miou"] - float(np.mean(np.nan_to_num(iou)))) <= 1e-12
+    rob = val_segformer_robust(m, batches, attack_iters=2)
+    assert np.isfinite(rob["miou"])
