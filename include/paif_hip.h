@@ -901,6 +901,49 @@ int paif_seafusion_sobel_bwd(const float* pack, int block, const void* sgn, floa
 int paif_seafusion_stem_bwd(const float* pack, int stream_id, const float* slab1, const float* d_slab1, float* d_x, int B, int H, int W,
                             paif_stream_t stream);
 
+/* DIDFuse baseline (fusion_model/AUIF.py of the reference, class DID; csrc/didfuse.hip, csrc/conv_slab.h).  fp32 throughout, NHWC maps.
+ * Streams: 0 x_over (AE_Encoder1), 1 x_under (AE_Encoder2).  enc [B,H,W,256] of a stream holds f1 | f2 | fB | fD (64 channels each);
+ * bd [B,H,W,128] = F_b | F_d, d1 [B,H,W,128] = Out1 | F_2, d2 [B,H,W,128] = Out2 | F_1, where F_* = 0.5 (stream 0 + stream 1) is
+ * written by stream 1's launches (stream 0's launch of the same layer must come first on the same HIP stream).  Gradient buffers: d_d2,
+ * d_d1, d_bd as their maps; dg [B,H,W,128] = d_f1 | d_f2 of one stream.  Matrix-core layers: 2 * stream + {0 cov2, 1 cov3 | cov4},
+ * 4 cov5, 5 cov6.  Every BatchNorm (eval mode) is folded into the pack; the PReLU slopes are arguments (>= 0: the reverse pass reads the
+ * branch off the taped output).  H, W >= 2 (reflection padding).  pack: paif_didfuse_pack_floats() floats, ZEROED, then written by eleven
+ * paif_didfuse_pack_conv calls.  No host synchronisation, no allocation: capturable.  Bit-reproducible (no atomics). */
+size_t paif_didfuse_pack_floats(void);
+/* One Conv2d with its BatchNorm2d into the kernels' layout: the weight times gamma * rsqrt(var + eps) per output channel, the bias
+ * beta + (b - mean) * that scale.  conv = 4 * stream + {0 cov1, 1 cov2, 2 cov3, 3 cov4}; 8 cov5, 9 cov6, 10 cov7.
+ * cov3 and cov4 of a stream share ONE 64 -> 128 launch: each of their two calls writes its half of the folded [128][64][9] weight and
+ * rebuilds both operand packs from the whole of it, so between the two calls (or with only one of them made) the other conv's half is
+ * the zeros of the zeroed buffer.  All eleven calls are to be made, in any order on one stream, before the first forward. */
+int paif_didfuse_pack_conv(const float* w, const float* b, const float* bn_weight, const float* bn_bias, const float* bn_mean,
+                           const float* bn_var, float eps, int conv, float* pack, paif_stream_t stream);
+/* fusion_model/AUIF.py:10-15: channels [0, 64) of enc = PReLU(BN(conv 3x3 1 -> 64 of the reflection-padded plane b at x + b * sb)).
+ * Stream 1 also reads stream 0's map enc0 and WRITES 0.5 (f1 + f1 of stream 0) into channels [64, 128) of d2; stream 0 passes null for
+ * both. */
+int paif_didfuse_stem_fwd(const float* x, size_t sb, const float* pack, int stream_id, float slope, float* enc, const float* enc0, float* d2,
+                          int B, int H, int W, paif_stream_t stream);
+/* act(BN(conv 3x3, zero pad 1)), an implicit GEMM on v_mfma_f32_16x16x4_f32.  Layers 0..3: in = out = the stream's enc; cov2 reads
+ * [0, 64), writes [64, 128) (PReLU, `slope`); cov3 | cov4 read [64, 128), write [128, 256) (tanh; `slope` is not used).  Layers 2, 3
+ * (stream 1) also read stream 0's enc (`pair`) and WRITE the mean into `avg`: d1[64:128) (layer 2), bd (layer 3); every other layer
+ * passes null for both.  4: bd -> d1[0:64); 5: d1 -> d2[0:64) (PReLU). */
+int paif_didfuse_conv_fwd(const float* pack, int layer, float slope, const float* in, float* out, const float* pair, float* avg, int B,
+                          int H, int W, paif_stream_t stream);
+/* fusion_model/AUIF.py:91-96: fused = sigmoid(BN(conv 3x3 128 -> 1 of the reflection-padded d2)). */
+int paif_didfuse_head_fwd(const float* pack, const float* d2, float* fused, int B, int H, int W, paif_stream_t stream);
+/* Reverse of cov7: d_fused * fused * (1 - fused) through the transposed conv and the transposed reflection; WRITES all of d_d2. */
+int paif_didfuse_head_bwd(const float* pack, const float* fused, const float* d_fused, float* d_d2, int B, int H, int W,
+                          paif_stream_t stream);
+/* Reverse of a matrix-core layer (input gradients).  5: taped d2, d_out d_d2 -> d_d1 (all 128 written); 4: taped d1, d_out d_d1 -> d_bd
+ * (written); 1, 3: taped = the stream's enc, d_out = d_bd (times 0.5 and tanh' from fB | fD) -> dg[64:128) (written); 0, 2: taped = the
+ * stream's enc, d_out = d_in = dg, d_skip = d_d1: dg[64:128) + 0.5 d_d1[64:128) through PReLU' (from f2) -> dg[0:64) (written).  d_skip is
+ * null for every other layer.  In that order. */
+int paif_didfuse_conv_bwd(const float* pack, int layer, float slope, const float* taped, const float* d_out, float* d_in,
+                          const float* d_skip, int B, int H, int W, paif_stream_t stream);
+/* Reverse of a stream's cov1: dg[0:64) + 0.5 d_d2[64:128) through PReLU' (from f1), the transposed conv and the transposed reflection
+ * -> d_x [B,H,W] (written). */
+int paif_didfuse_stem_bwd(const float* pack, int stream_id, float slope, const float* enc, const float* dg, const float* d_d2, float* d_x,
+                          int B, int H, int W, paif_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -237,6 +237,14 @@ SIGNATURES = {
     "paif_seafusion_tail_bwd": (c_int, [F, c_int, F, F, F, c_int, c_int, c_int, F]),
     "paif_seafusion_sobel_bwd": (c_int, [F, c_int, F, F, c_int, c_int, c_int, F]),
     "paif_seafusion_stem_bwd": (c_int, [F, c_int, F, F, F, c_int, c_int, c_int, F]),
+    "paif_didfuse_pack_floats": (c_size_t, []),
+    "paif_didfuse_pack_conv": (c_int, [F, F, F, F, F, F, c_float, c_int, F, F]),
+    "paif_didfuse_stem_fwd": (c_int, [F, c_size_t, F, c_int, c_float, F, F, F, c_int, c_int, c_int, F]),
+    "paif_didfuse_conv_fwd": (c_int, [F, c_int, c_float, F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_didfuse_head_fwd": (c_int, [F, F, F, c_int, c_int, c_int, F]),
+    "paif_didfuse_head_bwd": (c_int, [F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_didfuse_conv_bwd": (c_int, [F, c_int, c_float, F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_didfuse_stem_bwd": (c_int, [F, c_int, c_float, F, F, F, F, c_int, c_int, c_int, F]),
 }
 
 _lib = None

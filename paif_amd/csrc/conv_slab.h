@@ -3,7 +3,11 @@
 //   * TAPS: 9 (3 x 3, zero pad 1) or 1 (1 x 1: no halo is staged);
 //   * MB in {1, 2, 3, 4} blocks of 16 output channels per workgroup (plan_for(): a 16-channel output spends no instruction on zeros);
 //   * the LeakyReLU slope is an argument: of the store epilogue (EPI_ACT) or of the input mask (MASK);
-//   * EPI_ACT adds up to two biases (a 1 x 1 over two weight matrices side by side sums both convs' biases).
+//   * EPI_ACT adds up to two biases (a 1 x 1 over two weight matrices side by side sums both convs' biases);
+//   * ACT: the activation of the store epilogue and of the input mask is LeakyReLU (the default) or tanh (mask 1 - taped^2);
+//   * PAIR: the epilogue also reads the quad another map holds at the same place and stores the mean of the two into a third map;
+//   * XIN: the masked staging scales its input (1), and adds a scaled second input before the mask (2); the mask has its own stride.
+// The last three default to what the header did before them: an instantiation that does not name them compiles to the same code.
 // Everything else is conv_k's.  Output CHANNELS on M, 16 PIXELS of one image row on N; the D operand of lane l is channels
 // 4 (l >> 4) .. + 3 of pixel l & 15, one float4 of the NHWC map, and the B operand of four consecutive instructions is one float4 of the
 // input map.  A workgroup of four waves owns a 16 x 16 pixel tile (four rows per wave) and MB blocks of 16 output channels (blockIdx.y
@@ -22,6 +26,8 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 constexpr int DT = 16;   // tile edge: 4 waves x 4 rows of 16 pixels
 
 enum { EPI_ACT = 0, EPI_STORE = 1, EPI_ADD = 2 };
+enum { ACT_LEAKY = 0, ACT_TANH = 1 };
+enum { XIN_PLAIN = 0, XIN_SCALED = 1, XIN_SUM = 2 };
 
 // One operand pack: M output channels in `groups` groups of MB blocks of 16, K input channels in `chunks` chunks of 16, `taps` taps.
 struct Plan {
@@ -65,6 +71,15 @@ __device__ __forceinline__ float4 dleaky4(float4 f, float4 v, float s) {
   return make_float4(dleaky(f.x, v.x, s), dleaky(f.y, v.y, s), dleaky(f.z, v.z, s), dleaky(f.w, v.w, s));
 }
 
+// tanh' off the taped OUTPUT t: 1 - t^2, as (1 - t)(1 + t)
+__device__ __forceinline__ float dtanh(float t, float g) { return g * ((1.f - t) * (1.f + t)); }
+__device__ __forceinline__ float4 dtanh4(float4 t, float4 v) { return make_float4(dtanh(t.x, v.x), dtanh(t.y, v.y), dtanh(t.z, v.z), dtanh(t.w, v.w)); }
+template <int ACT>
+__device__ __forceinline__ float act_of(float v, float s) {
+  if constexpr (ACT == ACT_TANH) return tanhf(v);
+  else return leaky(v, s);
+}
+
 struct ConvArgs {
   const float* in;      // first channel of the input slice; pixel stride in_cs floats, nq channel quads
   const float* mask;    // MASK: the taped map of the same slice (same stride)
@@ -74,11 +89,21 @@ struct ConvArgs {
   const float* bias2;   // EPI_ACT: a second bias, or null
   float slope;          // LeakyReLU slope: of the stored map (EPI_ACT), of the taped map behind the input (MASK)
   int in_cs, nq, out_cs, out_off, out_n, chunks, H, W, tx, ty;
+  // PAIR: `pair` is laid out as `out` (same stride and offset); 0.5 (own + pair) goes to channels [avg_off, avg_off + out_n) of `avg`
+  const float* pair = nullptr;
+  float* avg = nullptr;
+  int avg_cs = 0, avg_off = 0;
+  // XIN: staged value = mask(in_scale * in [+ in2_scale * in2]); in2 has the stride of in, the mask its own (XIN_PLAIN: in_cs)
+  const float* in2 = nullptr;
+  float in_scale = 1.f, in2_scale = 1.f;
+  int mask_cs = 0;
 };
 
-template <int TAPS, int MB, bool MASK, int EPI>
+template <int TAPS, int MB, bool MASK, int EPI, int ACT = ACT_LEAKY, bool PAIR = false, int XIN = XIN_PLAIN>
 __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
   static_assert(TAPS == 9 || TAPS == 1, "3 x 3 or 1 x 1");
+  static_assert(!PAIR || EPI == EPI_ACT, "the pair store belongs to the activation epilogue");
+  static_assert(XIN == XIN_PLAIN || MASK, "the extended staging is the masked one");
   constexpr int HALO = TAPS == 9 ? 1 : 0, DP = DT + 2 * HALO;
   constexpr int QS = (DP * DP + 15) / 16 * 16;   // quad stride in float4, a multiple of 256 B: quad planes start at the same LDS bank
   __shared__ float4 s_x[4 * QS];
@@ -104,7 +129,19 @@ __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
       if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W && gq < a.nq) {
         const size_t o = (img + (size_t)gy * W + gx) * a.in_cs + 4 * gq;
         v = *reinterpret_cast<const float4*>(a.in + o);
-        if constexpr (MASK) v = dleaky4(*reinterpret_cast<const float4*>(a.mask + o), v, a.slope);
+        if constexpr (XIN != XIN_PLAIN) {
+          v = make_float4(a.in_scale * v.x, a.in_scale * v.y, a.in_scale * v.z, a.in_scale * v.w);
+          if constexpr (XIN == XIN_SUM) {
+            const float4 u = *reinterpret_cast<const float4*>(a.in2 + o);
+            v = make_float4(fmaf(a.in2_scale, u.x, v.x), fmaf(a.in2_scale, u.y, v.y), fmaf(a.in2_scale, u.z, v.z), fmaf(a.in2_scale, u.w, v.w));
+          }
+        }
+        if constexpr (MASK) {
+          const size_t om = XIN == XIN_PLAIN ? o : (img + (size_t)gy * W + gx) * a.mask_cs + 4 * gq;
+          const float4 f = *reinterpret_cast<const float4*>(a.mask + om);
+          if constexpr (ACT == ACT_TANH) v = dtanh4(f, v);
+          else v = dleaky4(f, v, a.slope);
+        }
       }
       s_x[sq * QS + pix] = v;
     }
@@ -149,10 +186,18 @@ __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
     for (int r = 0; r < 4; ++r) {
       const int gy = y0 + r0 + r;
       if (gy >= H) continue;
-      float4* o = reinterpret_cast<float4*>(a.out + (img + (size_t)gy * W + gx) * a.out_cs + a.out_off + co);   // owned by this lane
+      const size_t px = img + (size_t)gy * W + gx;
+      float4* o = reinterpret_cast<float4*>(a.out + px * a.out_cs + a.out_off + co);   // owned by this lane
       const f32x4 v = acc[mb][r];
       if constexpr (EPI == EPI_ACT) {
-        *o = make_float4(leaky(v[0] + bs.x, a.slope), leaky(v[1] + bs.y, a.slope), leaky(v[2] + bs.z, a.slope), leaky(v[3] + bs.w, a.slope));
+        const float4 f = make_float4(act_of<ACT>(v[0] + bs.x, a.slope), act_of<ACT>(v[1] + bs.y, a.slope), act_of<ACT>(v[2] + bs.z, a.slope),
+                                     act_of<ACT>(v[3] + bs.w, a.slope));
+        *o = f;
+        if constexpr (PAIR) {   // the other stream's quad at this place was stored by an earlier launch; the mean's quad is this lane's too
+          const float4 u = *reinterpret_cast<const float4*>(a.pair + px * a.out_cs + a.out_off + co);
+          *reinterpret_cast<float4*>(a.avg + px * a.avg_cs + a.avg_off + co) =
+              make_float4(0.5f * (u.x + f.x), 0.5f * (u.y + f.y), 0.5f * (u.z + f.z), 0.5f * (u.w + f.w));
+        }
       } else if constexpr (EPI == EPI_STORE) {
         *o = make_float4(v[0], v[1], v[2], v[3]);
       } else {
@@ -169,6 +214,11 @@ void launch_conv(int MB, dim3 grid, hipStream_t s, const ConvArgs& a) {
   else if (MB == 3) hipLaunchKernelGGL((conv_k<TAPS, 3, MASK, EPI>), grid, dim3(256), 0, s, a);
   else if (MB == 2) hipLaunchKernelGGL((conv_k<TAPS, 2, MASK, EPI>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((conv_k<TAPS, 1, MASK, EPI>), grid, dim3(256), 0, s, a);
+}
+// the 3 x 3, MB = 4 form with the later template parameters named
+template <bool MASK, int EPI, int ACT, bool PAIR, int XIN>
+void launch_conv4(dim3 grid, hipStream_t s, const ConvArgs& a) {
+  hipLaunchKernelGGL((conv_k<9, 4, MASK, EPI, ACT, PAIR, XIN>), grid, dim3(256), 0, s, a);
 }
 
 }  // namespace paif_slab

@@ -2401,3 +2401,84 @@ def seafusion_backward(maps, fused, d_fused, pack):
         _lib.check(L.paif_seafusion_stem_bwd(_p(pack), s, _p(slab1), _p(d_slab1), _p(d_x), B, H, W, _stream()), "seafusion_stem_bwd")
         grads.append(d_x)
     return grads[0], grads[1]
+
+
+# ---------------------------------------------------------------------------------------------
+# DIDFuse baseline (csrc/didfuse.hip, csrc/conv_slab.h; fusion_model/didfuse.py is the module)
+# ---------------------------------------------------------------------------------------------
+class DidfusePack:
+    """The packed weights of DIDFuse (BatchNorm folded in) and the six PReLU slopes as Python floats, in module order: per encoder cov1,
+    cov2; then cov5, cov6."""
+
+    __slots__ = ("weights", "slopes")
+
+    def __init__(self, weights, slopes):
+        self.weights, self.slopes = weights, tuple(float(s) for s in slopes)
+
+
+def didfuse_pack(convs, slopes):
+    """convs: the eleven (Conv2d weight, bias, BatchNorm2d weight, bias, running_mean, running_var, eps) in paif_amd.synthetic.DIDFUSE_CONVS
+    order; slopes: the six PReLU slopes (one-element tensors or floats), read to the host HERE, once per pack -> DidfusePack.  The fold
+    gamma * rsqrt(var + eps) runs on the device in fp32.  A negative slope is refused: the reverse pass reads the PReLU branch off the taped
+    output."""
+    if len(convs) != 11 or len(slopes) != 6:
+        raise ValueError("didfuse_pack: eleven convs and six PReLU slopes are expected, got %d and %d" % (len(convs), len(slopes)))
+    host = [float(s.detach().reshape(-1)[0]) if torch.is_tensor(s) else float(s) for s in slopes]
+    for k, s in enumerate(host):
+        if not s >= 0.0:
+            raise ValueError("DIDFuse: PReLU slope %d is %g; the reverse pass reads the branch off the taped output, which is right for "
+                             "slopes >= 0 only" % (k, s))
+    dev = convs[0][0].device
+    pack = torch.zeros(lib().paif_didfuse_pack_floats(), device=dev, dtype=torch.float32)
+    for conv, (w, b, g, be, mu, var, eps) in enumerate(convs):
+        ptrs = [_p(x.detach().contiguous()) for x in (w, b, g, be, mu, var)]
+        _lib.check(lib().paif_didfuse_pack_conv(*ptrs, float(eps), conv, _p(pack), _stream()), "didfuse_pack_conv")
+    return DidfusePack(pack, host)
+
+
+def didfuse_forward(x_over, x_under, pack):
+    """Two [B,1,H,W] planes -> (maps, fused [B,1,H,W]).  maps: enc [B,H,W,256] per stream (f1 | f2 | fB | fD; x_over first), bd = F_b | F_d,
+    d1 = Out1 | F_2, d2 = Out2 | F_1 [B,H,W,128], all fp32 NHWC.  Ten launches; the means are written by the second stream's launches."""
+    B, _, H, W = x_over.shape
+    L = lib()
+    dev = x_over.device
+    planes = [_plane(x_over), _plane(x_under)]
+    wp, sl = _p(pack.weights), pack.slopes
+
+    def new(c):
+        return torch.empty((B, H, W, c), device=dev, dtype=torch.float32)
+
+    enc, bd, d1, d2 = [new(256), new(256)], new(128), new(128), new(128)
+    fused = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    for s in range(2):
+        _, p, sb = planes[s]
+        e, pair = _p(enc[s]), (_p(enc[0]) if s else None)
+        _lib.check(L.paif_didfuse_stem_fwd(p, sb, wp, s, sl[2 * s], e, pair, _p(d2) if s else None, B, H, W, _stream()), "didfuse_stem_fwd")
+        _lib.check(L.paif_didfuse_conv_fwd(wp, 2 * s, sl[2 * s + 1], e, e, pair, _p(d1) if s else None, B, H, W, _stream()), "didfuse_conv_fwd")
+        _lib.check(L.paif_didfuse_conv_fwd(wp, 2 * s + 1, 0.0, e, e, pair, _p(bd) if s else None, B, H, W, _stream()), "didfuse_conv_fwd")
+    _lib.check(L.paif_didfuse_conv_fwd(wp, 4, sl[4], _p(bd), _p(d1), None, None, B, H, W, _stream()), "didfuse_conv_fwd")
+    _lib.check(L.paif_didfuse_conv_fwd(wp, 5, sl[5], _p(d1), _p(d2), None, None, B, H, W, _stream()), "didfuse_conv_fwd")
+    _lib.check(L.paif_didfuse_head_fwd(wp, _p(d2), _p(fused), B, H, W, _stream()), "didfuse_head_fwd")
+    return dict(enc=enc, bd=bd, d1=d1, d2=d2), fused
+
+
+def didfuse_backward(maps, fused, d_fused, pack):
+    """Reverse of didfuse_forward (input gradients) from the taped maps and fused plane -> (d_x_over, d_x_under) [B,1,H,W].  Nine
+    launches; nothing is recomputed and nothing needs a memset."""
+    B, _, H, W = fused.shape
+    L = lib()
+    d_fused = d_fused.contiguous()
+    wp, sl = _p(pack.weights), pack.slopes
+    d_d2, d_d1, d_bd, dg = (torch.empty_like(maps["bd"]) for _ in range(4))
+    _lib.check(L.paif_didfuse_head_bwd(wp, _p(fused), _p(d_fused), _p(d_d2), B, H, W, _stream()), "didfuse_head_bwd")
+    _lib.check(L.paif_didfuse_conv_bwd(wp, 5, sl[5], _p(maps["d2"]), _p(d_d2), _p(d_d1), None, B, H, W, _stream()), "didfuse_conv_bwd")
+    _lib.check(L.paif_didfuse_conv_bwd(wp, 4, sl[4], _p(maps["d1"]), _p(d_d1), _p(d_bd), None, B, H, W, _stream()), "didfuse_conv_bwd")
+    grads = []
+    for s in range(2):      # dg is reused: the second stream's launches follow the first's on the same HIP stream
+        e = _p(maps["enc"][s])
+        _lib.check(L.paif_didfuse_conv_bwd(wp, 2 * s + 1, 0.0, e, _p(d_bd), _p(dg), None, B, H, W, _stream()), "didfuse_conv_bwd")
+        _lib.check(L.paif_didfuse_conv_bwd(wp, 2 * s, sl[2 * s + 1], e, _p(dg), _p(dg), _p(d_d1), B, H, W, _stream()), "didfuse_conv_bwd")
+        d_x = torch.empty_like(fused)
+        _lib.check(L.paif_didfuse_stem_bwd(wp, s, sl[2 * s], e, _p(dg), _p(d_d2), _p(d_x), B, H, W, _stream()), "didfuse_stem_bwd")
+        grads.append(d_x)
+    return grads[0], grads[1]

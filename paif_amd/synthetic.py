@@ -192,6 +192,44 @@ def seafusion_state_dict(scales, shift):
     return sd
 
 
+# The eleven Conv2d + BatchNorm2d blocks of the DIDFuse baseline (reference fusion_model/AUIF.py, class DID) in module order, as
+# (nn.Sequential prefix, index of the conv in it, out channels, in channels, has a PReLU): the order of ops.didfuse_pack.  The conv is
+# followed by its BatchNorm and, where there is one, the PReLU; cov1 and cov7 start with the ReflectionPad2d.
+def _did_encoder(prefix):
+    return ((prefix + ".cov1.cov1", 1, 64, 1, True), (prefix + ".cov2.cov2", 0, 64, 64, True), (prefix + ".cov3.cov3", 0, 64, 64, False),
+            (prefix + ".cov4.cov4", 0, 64, 64, False))
+
+
+DIDFUSE_CONVS = (_did_encoder("AE_Encoder1") + _did_encoder("AE_Encoder2")
+                 + (("AE_Decoder1.cov5.cov5", 0, 64, 128, True), ("AE_Decoder1.cov6.cov6", 0, 64, 128, True),
+                    ("AE_Decoder1.cov7.cov7", 1, 1, 128, False)))
+DIDFUSE_SLOPES = (0.10, 0.15, 0.20, 0.25, 0.30, 0.35)   # the six PReLU slopes in module order
+
+
+def didfuse_state_dict(scales, shift):
+    """key -> numpy array (83 entries): formula_tensor("did/" + key) times the conv's scale (weight and bias alike), `shift` added to
+    cov7's conv bias, formula values (not the identity) for the BatchNorm entries, and the six PReLU slopes set to DIDFUSE_SLOPES in module
+    order (formula_tensor would take a one-element `weight` for a slope in [0.1, 0.3): the listed values are told apart more easily).
+    tools/make_golden_didfuse.py and the tests rebuild the fixture weights with this one expression."""
+    scales = np.asarray(scales, dtype=np.float32)
+    assert scales.shape == (len(DIDFUSE_CONVS),)
+    sd, slopes = {}, iter(DIDFUSE_SLOPES)
+    for (prefix, k, cout, cin, prelu), s in zip(DIDFUSE_CONVS, scales):
+        conv, bn = "%s.%d" % (prefix, k), "%s.%d" % (prefix, k + 1)
+        sd[conv + ".weight"] = formula_tensor("did/" + conv + ".weight", (cout, cin, 3, 3)) * s
+        sd[conv + ".bias"] = formula_tensor("did/" + conv + ".bias", (cout,)) * s
+        for leaf in ("weight", "bias", "running_mean", "running_var"):
+            sd["%s.%s" % (bn, leaf)] = formula_tensor("did/%s.%s" % (bn, leaf), (cout,))
+        if cout == 1:   # BatchNorm2d(1): a one-element `weight` is a norm gain here, not a slope
+            sd[bn + ".weight"] = (0.8 + 0.4 * hash_uniform(key_seed("did/" + bn + ".weight"), 1)).astype(np.float32)
+        sd[bn + ".num_batches_tracked"] = formula_tensor("did/" + bn + ".num_batches_tracked", ())
+        if prelu:
+            sd["%s.%d.weight" % (prefix, k + 2)] = np.array([next(slopes)], dtype=np.float32)
+    last = "AE_Decoder1.cov7.cov7.1.bias"
+    sd[last] = sd[last] + np.float32(shift)
+    return sd
+
+
 # --------------------------------------------------------------------------------------
 # inputs
 # --------------------------------------------------------------------------------------
