@@ -80,6 +80,13 @@ int paif_stem_fwd_twin(const float* img, size_t img_bstride, const float* w, con
  * either way. */
 int paif_stem_fwd_twin_f16(const float* img, size_t img_bstride, const float* w, const float* prelu, float* feat, float* feat_f16,
                            float* guide, int B, int H, int W, paif_stream_t stream);
+/* Pair form: stem_1 on img0 and stem_2 on img1 (each with its own batch stride, weights and slope) in ONE launch.  Outputs are joint
+ * tensors, problem p in images p*B .. p*B + B - 1: feat [2B,H,W,32] fp32 (may be NULL with twin = 2), feat16 [2B,H,W,32] `unsigned short`
+ * data (twin: 0 = none and feat16 NULL, 1 = bf16, 2 = IEEE fp16), guide [2B,H,W] (may be NULL).  Each half holds the bits of its own
+ * single call. */
+int paif_stem_fwd_pair(const float* img0, size_t img_bstride0, const float* w0, const float* prelu0, const float* img1, size_t img_bstride1,
+                       const float* w1, const float* prelu1, float* feat, float* feat16, int twin, float* guide, int B, int H, int W,
+                       paif_stream_t stream);
 /* Cell_Decom.get_residue on an existing NHWC [B,H,W,32] map (:517-521): guide = max_c - min_c. */
 int paif_channel_residue_fwd(const float* x, float* guide, int B, int H, int W, paif_stream_t stream);
 
@@ -123,6 +130,18 @@ int paif_guided_filter_fused_fwd_hf16(const float* guide, const float* y, float*
  * reference lines, core/model_fusion_auto.py:522-535). */
 int paif_guided_filter_fused_fwd_hf16_y16(const float* guide, const float* y16, float* hf, float eps0, float eps1, float* workspace,
                                           int B, int H, int W, paif_stream_t stream);
+
+/* Two problems of one geometry as ONE batch (the two image streams of the fusion forward): images 0 .. bsplit-1 are problem 0, images
+ * bsplit .. B-1 problem 1 (B = 2 * bsplit); guide / y / out are the joint tensors (out [2][B,H,W,32]).  out_mode: 0 fp32 LF, 1 bf16 LF, 2 fp16 HF, 3 fp16 HF
+ * with y read as fp16 (the four single entry points above).  The f16-range fallback is decided per problem: one problem's overflow
+ * never changes the other problem's bits, and each half holds the bits of its own single call wherever the two calls take the same
+ * engine.  (The range word also sees the partial window sums of a run's warm-up rows, and a joint call cuts the rows into other runs than
+ * a single call -- as single calls of different B already do -- so for mixed-sign data whose 9-row sums lie within a partial sum of the
+ * 65,000 bound one call may take the fallback where the other does not; either result is a correct filter output.)  paif_guided_filter_fused_joint_fits: 1 if the matrix-core engine takes the joint batch of B images; if
+ * not, the caller keeps two single calls. */
+int paif_guided_filter_fused_joint_fits(int B, int H, int W);
+int paif_guided_filter_fused_fwd_joint(const float* guide, const float* y, float* out, float eps0, float eps1, float* workspace, int B,
+                                       int bsplit, int H, int W, int out_mode, paif_stream_t stream);
 
 /* Dense k x k convolution, stride 1, "same" zero padding (pad = dil*(k-1)/2), Cout <= 32, inputs =
  * virtual concat of up to 3 NHWC sources of `cin` channels each, fp32 MFMA (v_mfma_f32_32x32x2_f32)
@@ -239,6 +258,13 @@ int paif_add_fwd_f16(const float* a, const float* b, float* out, size_t n, paif_
 
 int paif_conv2d_blocks(int B, int H, int W);
 int paif_conv2d_fwd(const paif_conv_desc* d, int B, int H, int W, paif_stream_t stream);
+/* The pair form: ONE launch for two descriptors of one geometry (the two image streams of the fusion forward) that plan to the same
+ * kernel and differ only in maps, weight pack, scale / shift / slopes, alpha and output.  Built for the LDS-DMA 1x1 and the LDS-DMA 3x3
+ * dilation-1 tile kernel with (sources, residual maps) = (1, 0), (2, 0), (3, 1) without a fused ChannelPool; bits of two
+ * paif_conv2d_fwd calls.  Returns PAIF_ENOSUP for any other two descriptors (the caller then issues two single launches);
+ * paif_conv2d_pair_kernel_name gives the kernel's name, or PAIF_ENOSUP likewise.  reverse_tiles is taken from d0. */
+int paif_conv2d_pair_kernel_name(const paif_conv_desc* d0, const paif_conv_desc* d1, int B, int H, int W, char* buf, int buflen);
+int paif_conv2d_fwd_pair(const paif_conv_desc* d0, const paif_conv_desc* d1, int B, int H, int W, paif_stream_t stream);
 /* 1 if the kernel paif_conv2d_fwd runs for this descriptor / shape writes d->cpool (the fused ChannelPool of its output), else 0. */
 int paif_conv2d_can_cpool(const paif_conv_desc* d, int B, int H, int W);
 /* ChannelPool of ONE NHWC-32 map into the interleaved [B,H,W,4] plane (comp_off = comp + 0 or + 2): comp_off[4 p] = max_c x, comp_off[4 p + 1] =

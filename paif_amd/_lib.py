@@ -39,6 +39,7 @@ SIGNATURES = {
     "paif_stem_fwd": (c_int, [F, c_size_t, F, F, F, F, c_int, c_int, c_int, F]),
     "paif_stem_fwd_twin": (c_int, [F, c_size_t, F, F, F, F, F, c_int, c_int, c_int, F]),
     "paif_stem_fwd_twin_f16": (c_int, [F, c_size_t, F, F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_stem_fwd_pair": (c_int, [F, c_size_t, F, F, F, c_size_t, F, F, F, F, c_int, F, c_int, c_int, c_int, F]),
     "paif_channel_residue_fwd": (c_int, [F, F, c_int, c_int, c_int, F]),
     "paif_guided_filter_ab_fwd": (c_int, [F, F, F, c_float, c_float, c_int, c_int, c_int, F]),
     "paif_guided_filter_lf_fwd": (c_int, [F, F, F, c_int, c_int, c_int, F]),
@@ -49,8 +50,12 @@ SIGNATURES = {
     "paif_guided_filter_fused_fwd_bf16": (c_int, [F, F, F, c_float, c_float, F, c_int, c_int, c_int, F]),
     "paif_guided_filter_fused_fwd_hf16": (c_int, [F, F, F, c_float, c_float, F, c_int, c_int, c_int, F]),
     "paif_guided_filter_fused_fwd_hf16_y16": (c_int, [F, F, F, c_float, c_float, F, c_int, c_int, c_int, F]),
+    "paif_guided_filter_fused_joint_fits": (c_int, [c_int, c_int, c_int]),
+    "paif_guided_filter_fused_fwd_joint": (c_int, [F, F, F, c_float, c_float, F, c_int, c_int, c_int, c_int, c_int, F]),
     "paif_conv2d_blocks": (c_int, [c_int, c_int, c_int]),
     "paif_conv2d_fwd": (c_int, [POINTER(ConvDesc), c_int, c_int, c_int, F]),
+    "paif_conv2d_pair_kernel_name": (c_int, [POINTER(ConvDesc), POINTER(ConvDesc), c_int, c_int, c_int, c_char_p, c_int]),
+    "paif_conv2d_fwd_pair": (c_int, [POINTER(ConvDesc), POINTER(ConvDesc), c_int, c_int, c_int, F]),
     "paif_conv2d_is_persistent": (c_int, [POINTER(ConvDesc), c_int, c_int, c_int]),
     "paif_conv2d_can_cpool": (c_int, [POINTER(ConvDesc), c_int, c_int, c_int]),
     "paif_rdb_fused_wpk_floats": (c_size_t, []),

@@ -10,7 +10,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
-from ..operations_m import OPS, BasicConv, Conv2dParams, PReLUParams, _HipOp, _PackCache, grad_anchor
+from ..operations_m import OPS, BasicConv, Conv2dParams, PReLUParams, ResidualDenseBlock, _HipOp, _PackCache, grad_anchor
 
 
 # ---------------------------------------------------------------------------------------------
@@ -95,11 +95,12 @@ class Cell_Chain(_HipOp):
             self._ops += [MixedOp(C, name)]
         self._indices = indices
 
-    def forward_nhwc(self, inp, res=(), tape=None, out_f32=False, cpool=None):
+    def forward_nhwc(self, inp, res=(), tape=None, out_f32=False, cpool=None, first=None):
         """out_f32 (fp16-storage inference forward): ask the last op for an fp32 output map (honoured where its kernel exists);
-        cpool = (comp, offset): the ChannelPool of the chain's output goes into comp[..., offset:offset+2] (MixedOp.forward_nhwc)."""
-        s1 = inp
-        for i in range(self._steps):
+        cpool = (comp, offset): the ChannelPool of the chain's output goes into comp[..., offset:offset+2] (MixedOp.forward_nhwc).
+        first: the first op's output, already computed (the pair form runs the two streams' first ops together); not for a one-op chain."""
+        s1 = inp if first is None else first
+        for i in range(0 if first is None else 1, self._steps):
             last = i == self._steps - 1
             s1 = self._ops[i].forward_nhwc(s1, ((inp,) + tuple(res)) if last else (), tape, out_f32=out_f32 and last,
                                            cpool=cpool if last else None)
@@ -142,11 +143,38 @@ class Cell_Decom(nn.Module):
     def get_residue(self, tensor):
         return ops.to_nchw_view(ops.channel_residue(ops.to_nhwc(tensor)).unsqueeze(-1))
 
-    def decomposition_nhwc(self, x, guide=None, want_ab=False, out_bf16=False):
-        """-> lf [2,B,H,W,32] (LF for eps 1e-3, 1e-4)."""
+    def decomposition_nhwc(self, x, guide=None, want_ab=False, out_bf16=False, bsplit=None):
+        """-> lf [2,B,H,W,32] (LF for eps 1e-3, 1e-4).  bsplit: x / guide are the joint tensors of both streams (ops.guided_filter_pair)."""
         if guide is None:
             guide = ops.channel_residue(x)
-        return ops.guided_filter_pair(guide, x, tuple(self.eps_list), want_ab=want_ab, out_bf16=out_bf16)
+        return ops.guided_filter_pair(guide, x, tuple(self.eps_list), want_ab=want_ab, out_bf16=out_bf16, bsplit=bsplit)
+
+    def pair_capable(self):
+        """The pair form of the shared prefix is for two chains that begin alike: a ResidualDenseBlock with k = 3, dilation 1 each
+        (looked up on the modules, not in the genotype)."""
+        firsts = [c._ops[0]._op for c in (self.chain, self.chain2) if c._steps > 0]
+        return len(firsts) == 2 and all(isinstance(o, ResidualDenseBlock) and (o.k, o.d) == (3, 1) for o in firsts)
+
+    def forward_pair_nhwc(self, feat, guide, fir, fvis, comp=None):
+        """forward_nhwc (inference, 16-bit storage) behind ops.stem_pair: feat / guide are the joint [2B,...] stem outputs, fir / fvis
+        the map's half-views.  The guided filter runs once on the joint batch; behind it the streams go on separately on the half-views."""
+        B = fir.shape[0]
+        lf16 = ops._ACT_BF16[0]
+        lf = self.decomposition_nhwc(feat, guide, out_bf16=lf16, bsplit=B)          # [2,2B,H,W,32]
+        (lf_ir0, lf_vis0), (lf_ir1, lf_vis1) = ops.pair_halves(lf[0], B), ops.pair_halves(lf[1], B)
+        pack1, pn = (ops.pack_decomp1x1_hf_weight, "_hf16") if lf16 is torch.float16 else (ops.pack_decomp1x1_weight, "")
+        w_lf = self._packs.get("lf" + pn, [self.conv1x1_lf.weight], lambda: pack1(self.conv1x1_lf.weight))
+        w_hf = self._packs.get("hf" + pn, [self.conv1x1_hf.weight], lambda: pack1(self.conv1x1_hf.weight))
+        lfm, hfm = ops.conv2d_pair(dict(srcs=[ops.cast_storage(fir, True), lf_ir0, lf_ir1], wpk=w_lf, kh=1, dil=1, shift=self.conv1x1_lf.bias),
+                                   dict(srcs=[ops.cast_storage(fvis, True), lf_vis0, lf_vis1], wpk=w_hf, kh=1, dil=1, shift=self.conv1x1_hf.bias))
+        # the two chains' first ResidualDenseBlocks (pair_capable()) conv by conv together, unless one of them is its chain's last op (its
+        # conv3 then carries the outer residuals and the ChannelPool) or the one-kernel block is switched on
+        f_ir = f_vis = None
+        if self.chain._steps > 1 and self.chain2._steps > 1 and not ops.CONFIG.get("rdb_fused", False):
+            f_ir, f_vis = ResidualDenseBlock.forward_pair_nhwc(self.chain._ops[0]._op, lfm, self.chain2._ops[0]._op, hfm)
+        ir_feature = self.chain.forward_nhwc(lfm, (fir,), None, cpool=None if comp is None else (comp, 0), first=f_ir)
+        vis_feature = self.chain2.forward_nhwc(hfm, (fvis,), None, cpool=None if comp is None else (comp, 2), first=f_vis)
+        return ir_feature, vis_feature
 
     @staticmethod
     def _cat_lf_hf(x, lf):
@@ -375,8 +403,16 @@ class Network_Fusion_Searched(nn.Module):
             if not torch.cuda.is_current_stream_capturing():
                 vis_feature.record_stream(main)
             del fvis, g_vis
-            agg = self.spa.blend_nhwc(ir_feature, vis_feature, comp=comp)
-            return self._tail_nhwc(self.chain.forward_nhwc(agg, (), None, out_f32=self._last_f32()))
+            return self._blend_tail_nhwc(ir_feature, vis_feature, comp)
+        if self._pair_path(tape, inter, ir.is_cuda) and ops.guided_filter_joint_fits(2 * ir.shape[0], ir.shape[2], ir.shape[3]):
+            # both streams' stems in one launch, their guided filters as one joint batch (ops.CONFIG["stream_pair"]): same bits, same
+            # stream, fewer launches -- a joint guided-filter call streams fewer warm-up rows than two calls
+            feat, guide, (fir, fvis) = ops.stem_pair(ir, self.stem_1[0].weight, self.stem_1[1].weight,
+                                                     vis, self.stem_2[0].weight, self.stem_2[1].weight)
+            comp = self._new_comp(ir)
+            ir_feature, vis_feature = self.decompation.forward_pair_nhwc(feat, guide, fir, fvis, comp)
+            del feat, guide
+            return self._blend_tail_nhwc(ir_feature, vis_feature, comp)
         fir, g_ir = ops.stem(ir, self.stem_1[0].weight, self.stem_1[1].weight)
         fvis, g_vis = ops.stem(vis, self.stem_2[0].weight, self.stem_2[1].weight)
         t_dec = None if tape is None else {}
@@ -406,6 +442,17 @@ class Network_Fusion_Searched(nn.Module):
         if inter is not None:
             inter.update(fir=fir, fvis=fvis, ir_feature=ir_feature, vis_feature=vis_feature, agg=agg, feature2=feature2)
         return out
+
+    def _blend_tail_nhwc(self, ir_feature, vis_feature, comp):
+        """Behind the two streams of an inference forward that keeps no intermediates: spatial blend, the last chain, stem_out + tanh."""
+        agg = self.spa.blend_nhwc(ir_feature, vis_feature, comp=comp)
+        return self._tail_nhwc(self.chain.forward_nhwc(agg, (), None, out_f32=self._last_f32()))
+
+    def _pair_path(self, tape, inter, is_cuda):
+        """Whether this forward runs the pair form of the two streams' shared prefix: inference (no tape, no `inter`), a 16-bit storage
+        mode, single-stream mode, the switch on, and two chains that begin alike (Cell_Decom.pair_capable)."""
+        return (tape is None and inter is None and is_cuda and bool(ops._ACT_BF16[0]) and not ops.CONFIG.get("two_stream", False)
+                and ops.CONFIG.get("stream_pair", True) and self.decompation.pair_capable())
 
     @staticmethod
     def _new_comp(img):

@@ -35,6 +35,25 @@ struct Args {
 //               fp32 from fp16 sources; no fused ChannelPool) as a row-streaming kernel.  Taken from 32,768 strip-rows (B * H * ceil(W / 32))
 //               and H >= 64.  Switch PAIF_CONV_DMA_ROWS, read per call: unset = that size rule, 0 = never, 1 = wherever the 32-bit addressing holds.
 enum Form { NONE, TILE, ONE_BY_ONE, ROWS };
+
+// The PAIR form: one launch runs two problems of one geometry (Args::B, H, W, source and residual counts, activation kind, format,
+// tile order are common); what differs per problem is this block.  The kernels that have it take the second problem's block as a
+// further kernel argument: a workgroup of the second half (of every XCD's workgroups in the tile kernel, of the grid in the 1x1)
+// copies it over its Args before anything else -- scalar moves of kernel arguments, nothing inside a stage or tile loop.
+struct Prob {
+  const void* src[3];
+  const void* res[3];
+  const void* wpk;
+  const float* scale;
+  const float* shift;
+  const float* prelu;
+  void* out;
+  float alpha;
+};
+// the forms with a pair kernel: ONE_BY_ONE; TILE 3x3 dilation 1 with 32 output channels and no fused ChannelPool for (sources, residual
+// maps) = (1, 0), (2, 0), (3, 1), up to 16,384 tiles per problem (the tile table holds 128 tiles of a workgroup, a problem has 128 workgroups)
+bool pair_capable(const Args& a);
+int launch_pair(const Args& a0, const Args& a1, hipStream_t st);   // both pair_capable() and alike in everything but Prob's fields (the caller checks)
 Form classify(const Args& a);
 bool can_cpool(const Args& a);             // the TILE instantiations that write Args::cpool
 int launch(const Args& a, hipStream_t st);   // the form classify() names; PAIF_ENOSUP for NONE

@@ -101,8 +101,10 @@ struct Sched {
 // DIL: dilation (1, 2).  IA: input activation on the A fragments as they arrive from LDS (0 none; 2 ReLU -- max(x, 0) of a stored 16-bit
 // value is a 16-bit value: one v_pk_max_i16 per register, issued behind the MFMA in front of the fragment's first use): the composed
 // DilConv (ReLU -> depthwise 3x3 dilation 2 -> 1x1 -> BN, operations_m.py:494-506, as ONE dense dilated conv) is <1, NRES, F, CP, 2, 2>.
+// pair (conv_dma.h Prob): two problems in one launch -- each takes HALF of the workgroups of every XCD, so a problem's XCD-contiguous tile
+// ranges and the `reverse` order are those of a single launch on half the workgroups; ntiles is per problem.
 template <int NSRC, int NRES, int F, bool CP = false, int DIL = 1, int IA = 0>
-__global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, int tilesX, int tilesY) {
+__global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, int tilesX, int tilesY, Prob p1, int pair) {
   typedef Geo<DIL> G;
   constexpr int TWH = G::TWH, NPIX = G::NPIX, DPW = G::DPW, SLOT = G::SLOT, PF = G::PF, NSLOT = G::NSLOT, ROWB = G::ROWB, PARK_OFF = G::PARK_OFF;
   typedef Sched<NSRC, NRES, PF, DPW> SC;
@@ -125,7 +127,17 @@ __global__ __launch_bounds__(256, 1) void conv3x3_h16_dma(Args a, int ntiles, in
   const int wb = G::base_row(w);        // this wave's output rows: wb and wb + DIL
 
   // this workgroup's tiles: XCD x owns the contiguous range [x * tpx, (x + 1) * tpx); its workgroups interleave over it
-  const int xcd = blockIdx.x & 7, wg = blockIdx.x >> 3, nwg = gridDim.x >> 3;
+  const int xcd = blockIdx.x & 7;
+  int wg = blockIdx.x >> 3, nwg = gridDim.x >> 3;
+  if (!CP && DIL == 1 && pair) {       // workgroup-uniform: the second half of this XCD's workgroups runs problem 1
+    nwg >>= 1;
+    if (wg >= nwg) {
+      wg -= nwg;
+#pragma unroll
+      for (int s = 0; s < 3; ++s) { a.src[s] = p1.src[s]; a.res[s] = p1.res[s]; }
+      a.wpk = p1.wpk; a.scale = p1.scale; a.shift = p1.shift; a.prelu = p1.prelu; a.out = p1.out; a.alpha = p1.alpha;
+    }
+  }
   const int tpx = (ntiles + 7) >> 3;
   const int t_beg = xcd * tpx, t_end = min(ntiles, t_beg + tpx);
   const int cnt = t_beg + wg < t_end ? (t_end - t_beg - wg + nwg - 1) / nwg : 0;
@@ -858,17 +870,38 @@ int launch_n(const Args& a, hipStream_t st) {
   const int tilesX = (a.W + TW - 1) / TW, tilesY = (a.H + TH - 1) / TH;
   if (a.cpool) {
     if constexpr (NSRC == 3 && (NRES == 1 || NRES == 3)) {      // can_cpool(): the last conv of a ResidualDenseBlock, inside a chain or closing it
-      if (a.f16) hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 2, true>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY);
-      else hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 1, true>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY);
+      if (a.f16) hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 2, true>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY, Prob{}, 0);
+      else hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 1, true>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY, Prob{}, 0);
     } else {
       paif::set_error("conv2d(dma): the fused ChannelPool is built for 3 sources with 1 or 3 residual maps");
       return PAIF_ENOSUP;
     }
-  } else if (a.f16) hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 2>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY);
-  else hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 1>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY);
+  } else if (a.f16) hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 2>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY, Prob{}, 0);
+  else hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 1>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY, Prob{}, 0);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     paif::set_error("conv2d(h16 dma): launch failed: %s", hipGetErrorString(e));
+    return (int)e;
+  }
+  return 0;
+}
+
+static Prob prob_of(const Args& a) {
+  Prob p{};
+  for (int s = 0; s < 3; ++s) { p.src[s] = a.src[s]; p.res[s] = a.res[s]; }
+  p.wpk = a.wpk; p.scale = a.scale; p.shift = a.shift; p.prelu = a.prelu; p.out = a.out; p.alpha = a.alpha;
+  return p;
+}
+
+template <int NSRC, int NRES>
+int launch_n_pair(const Args& a0, const Args& a1, hipStream_t st) {
+  const int tilesX = (a0.W + TW - 1) / TW, tilesY = (a0.H + TH - 1) / TH;
+  const Prob p1 = prob_of(a1);
+  if (a0.f16) hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 2>), dim3(256), dim3(256), 0, st, a0, a0.B * tilesX * tilesY, tilesX, tilesY, p1, 1);
+  else hipLaunchKernelGGL((conv3x3_h16_dma<NSRC, NRES, 1>), dim3(256), dim3(256), 0, st, a0, a0.B * tilesX * tilesY, tilesX, tilesY, p1, 1);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    paif::set_error("conv2d(h16 dma, pair): launch failed: %s", hipGetErrorString(e));
     return (int)e;
   }
   return 0;
@@ -879,8 +912,8 @@ int launch_n(const Args& a, hipStream_t st) {
 template <int NRES, bool CP>
 int launch_d2(const Args& a, hipStream_t st) {
   const int tilesX = (a.W + TW - 1) / TW, tilesY = (a.H + TH - 1) / TH;
-  if (a.f16) hipLaunchKernelGGL((conv3x3_h16_dma<1, NRES, 2, CP, 2, 2>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY);
-  else hipLaunchKernelGGL((conv3x3_h16_dma<1, NRES, 1, CP, 2, 2>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY);
+  if (a.f16) hipLaunchKernelGGL((conv3x3_h16_dma<1, NRES, 2, CP, 2, 2>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY, Prob{}, 0);
+  else hipLaunchKernelGGL((conv3x3_h16_dma<1, NRES, 1, CP, 2, 2>), dim3(256), dim3(256), 0, st, a, a.B * tilesX * tilesY, tilesX, tilesY, Prob{}, 0);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     paif::set_error("conv2d(h16 dma, dilation 2): launch failed: %s", hipGetErrorString(e));
@@ -927,6 +960,32 @@ Form classify(const Args& a) {
   if (is_1x1(a)) return ONE_BY_ONE;
   if (is_rows(a)) return ROWS;
   return is_tile(a) ? TILE : NONE;
+}
+
+bool pair_capable(const Args& a) {
+  switch (classify(a)) {
+    case ONE_BY_ONE: return true;
+    case TILE: break;
+    default: return false;
+  }
+  const long long tiles = (long long)a.B * ((a.H + TH - 1) / TH) * ((a.W + TW - 1) / TW);
+  const int key = a.nsrc * 10 + a.nres;
+  return a.kh == 3 && a.dil == 1 && a.cout == 32 && !a.cpool && (key == 10 || key == 20 || key == 31) && tiles <= 128 * 128;
+}
+
+int launch_1x1_pair(const Args& a0, const Prob& p1, hipStream_t st);
+
+int launch_pair(const Args& a0, const Args& a1, hipStream_t st) {
+  if (!pair_capable(a0) || !pair_capable(a1) || classify(a0) != classify(a1) || a0.nsrc != a1.nsrc || a0.nres != a1.nres) {
+    paif::set_error("conv2d(h16 dma, pair): no pair kernel for these two descriptors");
+    return PAIF_ENOSUP;
+  }
+  if (classify(a0) == ONE_BY_ONE) return launch_1x1_pair(a0, prob_of(a1), st);
+  switch (a0.nsrc * 10 + a0.nres) {
+    case 10: return launch_n_pair<1, 0>(a0, a1, st);
+    case 20: return launch_n_pair<2, 0>(a0, a1, st);
+    default: return launch_n_pair<3, 1>(a0, a1, st);
+  }
 }
 
 bool can_cpool(const Args& a) {

@@ -48,7 +48,8 @@ static_assert(PF == 3, "a stage's DMA target is the same source of the next tile
 
 // F: 16-bit format of maps and weights (1 bf16, 2 fp16)
 template <int F>
-__global__ __launch_bounds__(WAVES * 64, 2) void conv_h16_dma_1x1(Args a, int ntiles) {
+// pair (conv_dma.h Prob): the second half of the grid runs problem 1; ntiles is per problem
+__global__ __launch_bounds__(WAVES * 64, 2) void conv_h16_dma_1x1(Args a, int ntiles, Prob p1, int pair) {
   __shared__ __attribute__((aligned(16))) unsigned char smem[LDS_BYTES];
   asm volatile("" ::"v"((unsigned)(uintptr_t)(__attribute__((address_space(3))) unsigned char*)smem) : "memory");   // only asm touches it
 
@@ -56,7 +57,17 @@ __global__ __launch_bounds__(WAVES * 64, 2) void conv_h16_dma_1x1(Args a, int nt
   const int w = __builtin_amdgcn_readfirstlane(tid >> 6);
   const int p = l & 31, hh = l >> 5;
   // this wave's tiles: gw, gw + nw, gw + 2 nw, ... (neighbouring waves stream neighbouring 4 KB runs of each map)
-  const int gw = blockIdx.x * WAVES + w, nw = gridDim.x * WAVES;
+  int bid = blockIdx.x, nblk = gridDim.x;      // workgroup-uniform
+  if (pair) {
+    nblk >>= 1;
+    if (bid >= nblk) {
+      bid -= nblk;
+#pragma unroll
+      for (int s = 0; s < 3; ++s) a.src[s] = p1.src[s];
+      a.wpk = p1.wpk; a.scale = p1.scale; a.shift = p1.shift; a.prelu = p1.prelu; a.out = p1.out; a.alpha = p1.alpha;
+    }
+  }
+  const int gw = bid * WAVES + w, nw = nblk * WAVES;
   if (gw >= ntiles) return;                    // (no barrier anywhere: a wave may leave on its own)
   const int cnt = (ntiles - gw + nw - 1) / nw;
 
@@ -212,11 +223,25 @@ bool is_1x1(const Args& a) {
 int launch_1x1(const Args& a, hipStream_t st) {
   const long long px = (long long)a.B * a.H * a.W;
   const int ntiles = (int)((px + TP - 1) / TP);
-  if (a.f16) hipLaunchKernelGGL(conv_h16_dma_1x1<2>, dim3(GRID), dim3(WAVES * 64), 0, st, a, ntiles);
-  else hipLaunchKernelGGL(conv_h16_dma_1x1<1>, dim3(GRID), dim3(WAVES * 64), 0, st, a, ntiles);
+  if (a.f16) hipLaunchKernelGGL(conv_h16_dma_1x1<2>, dim3(GRID), dim3(WAVES * 64), 0, st, a, ntiles, Prob{}, 0);
+  else hipLaunchKernelGGL(conv_h16_dma_1x1<1>, dim3(GRID), dim3(WAVES * 64), 0, st, a, ntiles, Prob{}, 0);
   hipError_t e = hipGetLastError();
   if (e != hipSuccess) {
     paif::set_error("conv2d(h16 dma 1x1): launch failed: %s", hipGetErrorString(e));
+    return (int)e;
+  }
+  return 0;
+}
+
+// two problems of one geometry: the same grid, half of it per problem
+int launch_1x1_pair(const Args& a, const Prob& p1, hipStream_t st) {
+  const long long px = (long long)a.B * a.H * a.W;
+  const int ntiles = (int)((px + TP - 1) / TP);
+  if (a.f16) hipLaunchKernelGGL(conv_h16_dma_1x1<2>, dim3(GRID), dim3(WAVES * 64), 0, st, a, ntiles, p1, 1);
+  else hipLaunchKernelGGL(conv_h16_dma_1x1<1>, dim3(GRID), dim3(WAVES * 64), 0, st, a, ntiles, p1, 1);
+  hipError_t e = hipGetLastError();
+  if (e != hipSuccess) {
+    paif::set_error("conv2d(h16 dma 1x1, pair): launch failed: %s", hipGetErrorString(e));
     return (int)e;
   }
   return 0;

@@ -2090,6 +2090,17 @@ static int plan_launch(const ConvPlan& p, const ConvArgs& a, hipStream_t st) {
   return launch_key<FAM_F32>(p, a, st);
 }
 
+// The pair form behind the same plan: two descriptors that plan to the same LDS-DMA kernel, one with a pair form (conv_dma.h
+// pair_capable), and that differ in nothing but the per-problem fields (maps, weights, scale / shift / slope, alpha, output).
+static bool plan_pair(const ConvPlan& p0, const ConvArgs& a0, const ConvPlan& p1, const ConvArgs& a1) {
+  if (p0.family != FAM_SPLIT || p1.family != FAM_SPLIT || p0.variant != CV_DMA || p1.variant != CV_DMA) return false;
+  if (p0.kh != p1.kh || p0.dil != p1.dil || p0.cin != p1.cin || p0.nres != p1.nres || p0.fmt != p1.fmt || p0.st != p1.st) return false;
+  if (a0.nsrc != a1.nsrc || a0.act != a1.act || a0.in_act != a1.in_act || a0.cout != a1.cout || a0.st != a1.st || a0.wl0 != a1.wl0) return false;
+  if (a0.cpool || a1.cpool || a0.pool_partial || a1.pool_partial) return false;
+  if ((a0.scale == nullptr) != (a1.scale == nullptr) || (a0.shift == nullptr) != (a1.shift == nullptr)) return false;
+  return paif_conv_dma::pair_capable(dma_args(a0, p0.kh, p0.dil)) && paif_conv_dma::pair_capable(dma_args(a1, p1.kh, p1.dil));
+}
+
 }  // namespace
 
 extern "C" {
@@ -2115,7 +2126,7 @@ int paif_conv2d_kernel_name(const paif_conv_desc* d, int B, int H, int W, char* 
   return 0;
 }
 
-int paif_conv2d_fwd(const paif_conv_desc* d, int B, int H, int W, paif_stream_t stream) {
+static int check_desc(const paif_conv_desc* d, int B, int H, int W) {
   PAIF_REQUIRE(d && d->out && d->wpk, PAIF_EINVAL, "conv2d: null descriptor/out/wpk");
   PAIF_REQUIRE(d->nsrc >= 1 && d->nsrc <= 3, PAIF_EINVAL, "conv2d: nsrc=%d", d->nsrc);
   for (int s = 0; s < d->nsrc; ++s) PAIF_REQUIRE(d->src[s], PAIF_EINVAL, "conv2d: src[%d] null", s);
@@ -2146,8 +2157,31 @@ int paif_conv2d_fwd(const paif_conv_desc* d, int B, int H, int W, paif_stream_t 
                    d->precision == PAIF_CONV_F16X3, PAIF_EINVAL,
                "conv2d: precision=%d", d->precision);
   PAIF_REQUIRE((d->precision != PAIF_CONV_BF16X6 && d->precision != PAIF_CONV_F16X3) || d->cin == 32, PAIF_ENOSUP, "conv2d: bf16x6 / f16x3 need 32-channel sources");
+  return 0;
+}
+
+int paif_conv2d_fwd(const paif_conv_desc* d, int B, int H, int W, paif_stream_t stream) {
+  if (const int rc = check_desc(d, B, H, W)) return rc;
   const ConvArgs a = conv_args(d, B, H, W);
   return plan_launch(plan_conv(a, d), a, paif::as_stream(stream));
+}
+
+int paif_conv2d_pair_kernel_name(const paif_conv_desc* d0, const paif_conv_desc* d1, int B, int H, int W, char* buf, int buflen) {
+  PAIF_REQUIRE(d0 && d1 && buf && buflen > 0 && B > 0 && H > 0 && W > 0, PAIF_EINVAL, "conv2d_pair_kernel_name: bad arguments");
+  const ConvArgs a0 = conv_args(d0, B, H, W), a1 = conv_args(d1, B, H, W);
+  const ConvPlan p0 = plan_conv(a0, d0), p1 = plan_conv(a1, d1);
+  PAIF_REQUIRE(plan_pair(p0, a0, p1, a1), PAIF_ENOSUP, "conv2d_pair: the two descriptors do not plan to one pair-capable kernel");
+  plan_name(p0, a0, buf, buflen);
+  return 0;
+}
+
+int paif_conv2d_fwd_pair(const paif_conv_desc* d0, const paif_conv_desc* d1, int B, int H, int W, paif_stream_t stream) {
+  if (const int rc = check_desc(d0, B, H, W)) return rc;
+  if (const int rc = check_desc(d1, B, H, W)) return rc;
+  const ConvArgs a0 = conv_args(d0, B, H, W), a1 = conv_args(d1, B, H, W);
+  const ConvPlan p0 = plan_conv(a0, d0), p1 = plan_conv(a1, d1);
+  PAIF_REQUIRE(plan_pair(p0, a0, p1, a1), PAIF_ENOSUP, "conv2d_pair: the two descriptors do not plan to one pair-capable kernel");
+  return paif_conv_dma::launch_pair(dma_args(a0, p0.kh, p0.dil), dma_args(a1, p1.kh, p1.dil), paif::as_stream(stream));
 }
 
 int paif_pack_conv_weight_bf16x3(const float* w, float* wpk, int cout, int nsrc, int kh, paif_stream_t stream) {

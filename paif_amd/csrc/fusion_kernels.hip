@@ -79,8 +79,18 @@ constexpr int STEM_GRID = PAIF_STEM_GRID;   // workgroups of a launch: 16 per CU
 __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ img, const float* __restrict__ w,
                                                    const float* __restrict__ prelu, float* __restrict__ feat,
                                                    float* __restrict__ guide, int B, int H, int W,
-                                                   size_t img_bstride, int chunks, unsigned short* __restrict__ feat16, int twin_f16) {
+                                                   size_t img_bstride, int chunks, unsigned short* __restrict__ feat16, int twin_f16,
+                                                   const float* __restrict__ img1, const float* __restrict__ w1,
+                                                   const float* __restrict__ prelu1, size_t img_bstride1) {
   const int q = threadIdx.x & 7;
+  // Pair form (img1 != NULL): two problems of one geometry in one launch -- the second half of the grid takes image set 1 with its own
+  // weights, slope and batch stride and writes rows B*H .. 2*B*H - 1 of the joint [2B,H,W,..] outputs.  A workgroup stays inside one
+  // problem (its 36 weights per thread are loaded once, as in the single form) and grid-strides over that problem's items.
+  int bid = blockIdx.x, nblk = gridDim.x, row_off = 0;   // block-uniform
+  if (img1 != nullptr) {
+    nblk >>= 1;
+    if (bid >= nblk) { bid -= nblk; img = img1; w = w1; prelu = prelu1; img_bstride = img_bstride1; row_off = B * H; }
+  }
   float wr[4][9];
 #pragma unroll
   for (int c = 0; c < 4; ++c)
@@ -96,7 +106,7 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ img
   __shared__ float patch[2][3][STEM_CHUNK + 2];
   const int nitems = B * H * chunks;
   int par = 0;
-  for (int item = blockIdx.x; item < nitems; item += gridDim.x, par ^= 1) {
+  for (int item = bid; item < nitems; item += nblk, par ^= 1) {
   const int chunk = item % chunks;
   const int row = item / chunks;       // b * H + y
   const int y = row % H, b = row / H;
@@ -110,9 +120,10 @@ __global__ __launch_bounds__(256) void stem_kernel(const float* __restrict__ img
   }
   __syncthreads();   // the only barrier of an item: a wave that writes buffer p again (two items later) has passed the NEXT item's barrier,
                      // which every wave reaches only after its reads of p
-  float* frow = feat ? feat + (size_t)row * W * 32 : nullptr;   // (NULL with a 16-bit twin, round 6: the fp16 forward keeps the twin only)
-  unsigned short* frow16 = feat16 ? feat16 + (size_t)row * W * 32 : nullptr;   // optional 16-bit twin of the map (bf16 / fp16 storage modes)
-  float* grow = guide ? guide + (size_t)row * W : nullptr;
+  const int orow = row + row_off;       // row of the (joint) outputs
+  float* frow = feat ? feat + (size_t)orow * W * 32 : nullptr;   // (NULL with a 16-bit twin, round 6: the fp16 forward keeps the twin only)
+  unsigned short* frow16 = feat16 ? feat16 + (size_t)orow * W * 32 : nullptr;   // optional 16-bit twin of the map (bf16 / fp16 storage modes)
+  float* grow = guide ? guide + (size_t)orow * W : nullptr;
 #pragma unroll
   for (int it = 0; it < STEM_CHUNK / 32; ++it) {
     const int xi = it * 32 + (threadIdx.x >> 3);
@@ -758,8 +769,26 @@ static int stem_launch(const float* img, size_t img_bstride, const float* w, con
   const int chunks = (W + STEM_CHUNK - 1) / STEM_CHUNK;
   PAIF_REQUIRE((size_t)B * H * chunks < ((size_t)1 << 31), PAIF_EINVAL, "stem: %dx%dx%d is too large for one launch", B, H, W);
   hipLaunchKernelGGL(stem_kernel, dim3((unsigned)min(B * H * chunks, STEM_GRID)), dim3(256), 0, paif::as_stream(stream), img, w,
-                     prelu, feat, guide, B, H, W, img_bstride, chunks, feat16, twin_f16);
+                     prelu, feat, guide, B, H, W, img_bstride, chunks, feat16, twin_f16, nullptr, nullptr, nullptr, (size_t)0);
   PAIF_LAUNCH_CHECK("stem");
+  return 0;
+}
+
+// Both image streams in one launch (the pair form of stem_kernel): outputs are the joint [2B,H,W,..] tensors, problem p in rows p*B ..
+int paif_stem_fwd_pair(const float* img0, size_t img_bstride0, const float* w0, const float* prelu0, const float* img1, size_t img_bstride1,
+                       const float* w1, const float* prelu1, float* feat, float* feat16, int twin, float* guide, int B, int H, int W,
+                       paif_stream_t stream) {
+  PAIF_REQUIRE(img0 && w0 && prelu0 && img1 && w1 && prelu1 && (feat || feat16) && B > 0 && H > 0 && W > 0, PAIF_EINVAL,
+               "stem_pair: bad arguments");
+  PAIF_REQUIRE((twin == 0) == (feat16 == nullptr) && twin >= 0 && twin <= 2, PAIF_EINVAL,
+               "stem_pair: twin must be 0 (none, feat16 NULL), 1 (bf16) or 2 (fp16)");
+  PAIF_REQUIRE(img_bstride0 >= (size_t)H * W && img_bstride1 >= (size_t)H * W, PAIF_EINVAL, "stem_pair: batch stride < H*W");
+  const int chunks = (W + STEM_CHUNK - 1) / STEM_CHUNK;
+  PAIF_REQUIRE((size_t)2 * B * H * chunks < ((size_t)1 << 31), PAIF_EINVAL, "stem_pair: 2x%dx%dx%d is too large for one launch", B, H, W);
+  const int per = min(B * H * chunks, STEM_GRID / 2);   // workgroups per problem
+  hipLaunchKernelGGL(stem_kernel, dim3((unsigned)(2 * per)), dim3(256), 0, paif::as_stream(stream), img0, w0, prelu0, feat, guide, B, H, W,
+                     img_bstride0, chunks, reinterpret_cast<unsigned short*>(feat16), twin == 2 ? 1 : 0, img1, w1, prelu1, img_bstride1);
+  PAIF_LAUNCH_CHECK("stem_pair");
   return 0;
 }
 

@@ -181,7 +181,7 @@ template <int OM>
 __global__ __launch_bounds__(64 * NW, GF2_MINW) void gf2_kernel(const float* __restrict__ guide, const float* __restrict__ y,
                                                      const float* __restrict__ planes, float* __restrict__ lf,
                                                      unsigned* __restrict__ flag, int B, int H, int W, int nstrip, int nslots,
-                                                     int rows_per_slot, int total_rows) {
+                                                     int rows_per_slot, int total_rows, int bsplit) {
   // halo fragments: [parity][quantity][slot = wave + 1; slots 0 and NW + 1 stay zero][lane]
 #if GF2_PAIRED
   __shared__ u32x4 hbuf[2][NQ / 2][NW + 2][64];                    // pairs (y, g y), (A0, b0), (A1, b1)
@@ -586,22 +586,24 @@ __global__ __launch_bounds__(64 * NW, GF2_MINW) void gf2_kernel(const float* __r
     step(std::integral_constant<int, 5>{}, itb);
   }
   __syncthreads();                                       // the next piece rewrites the 1 / ny table and starts on halo buffer 0
-  }   // pieces
-
-  // a 9-row sum beyond the f16 range cannot be split: tell the host wrapper's fallback launch
+  // a 9-row sum beyond the f16 range cannot be split: tell the host wrapper's fallback launch.  Once per PIECE (a piece lies inside one
+  // image), into the word of the image's problem: images b >= bsplit are the second problem of a joint call, whose overflow must not
+  // switch the first problem's output to the fallback's bits (and the other way round).  bsplit = B: one problem, word 0.
 #pragma unroll
   for (int m = 32; m >= 1; m >>= 1) vmax = fmaxf(vmax, __shfl_xor(vmax, m));
-  if (l == 0 && !(vmax < 65000.f)) atomicOr(flag, 1u);
+  if (l == 0 && !(vmax < 65000.f)) atomicOr(flag + (b >= bsplit ? 1 : 0), 1u);
+  vmax = 0.f;
+  }   // pieces
 }
 
 // what the host launcher (guided_filter.hip) needs to know about the build
 extern const int kStripOut = SO, kThreads = 64 * NW;
 
 #if GF2_NW < 12
-template __global__ void gf2_kernel<0>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
-template __global__ void gf2_kernel<1>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
+template __global__ void gf2_kernel<0>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
+template __global__ void gf2_kernel<1>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
 #endif
-template __global__ void gf2_kernel<2>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
-template __global__ void gf2_kernel<3>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
+template __global__ void gf2_kernel<2>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
+template __global__ void gf2_kernel<3>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
 
 }  // namespace GF2_NS

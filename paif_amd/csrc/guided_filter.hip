@@ -236,13 +236,13 @@ __device__ __forceinline__ void lds_barrier() {
 // its VALU instructions, a fifth of its LDS operations and one of its three divisions per row).
 constexpr int GT = 32, GH = GT + 2 * R;   // 32 x 32 output tile, 40 x 40 halo tile
 // Output: four [B*H*W] planes -- mean_g, 1/(var_g + eps0), 1/(var_g + eps1), 1/n -- each read as 16-byte column groups by the
-// matrix-core kernel (gf_mfma2.hip); block 0 also clears the f16-range flag behind the planes.
+// matrix-core kernel (gf_mfma2.hip); block 0 also clears the two f16-range flag words (one per problem of a joint call) behind the planes.
 __global__ __launch_bounds__(256) void gf_guide_stats_kernel(const float* __restrict__ guide, float* __restrict__ gs, unsigned* __restrict__ flag,
                                                              float eps0, float eps1, int B, int H, int W, int tilesX, int tilesY) {
   __shared__ float sG[GH][GH + 1];
   __shared__ float sH[GH][GT + 1], sH2[GH][GT + 1];
   int t = blockIdx.x;
-  if (t == 0 && threadIdx.x == 0) *flag = 0u;
+  if (t == 0 && threadIdx.x < 2) flag[threadIdx.x] = 0u;
   const int tx = t % tilesX; t /= tilesX;
   const int ty = t % tilesY;
   const int b = t / tilesY;
@@ -316,14 +316,16 @@ template <typename V> __device__ __forceinline__ V vfma(float s, V a, V c) {
 template <typename V, int NL>
 __global__ __launch_bounds__(FC * NL) void gf_fused_kernel(const float* __restrict__ guide, const float* __restrict__ y,
                                                            const float* __restrict__ gs, const unsigned* __restrict__ only_if, float* __restrict__ lf,
-                                                           int B, int H, int W, int nstrip, int nseg, int frows, int out_bf16) {
+                                                           int B, int H, int W, int nstrip, int nseg, int frows, int out_bf16, int bsplit) {
   constexpr int VW = VecOps<V>::VW;
   // out_bf16 == 3 (round 6): as 2 (fp16 high-frequency output), with y an IEEE fp16 map (the stem's 16-bit twin)
   const bool y_f16 = out_bf16 == 3;
   if (y_f16) out_bf16 = 2;
   const unsigned short* const y16 = reinterpret_cast<const unsigned short*>(y) + (blockIdx.z * NL + threadIdx.x % NL) * VW;
   unsigned short* const lf16 = reinterpret_cast<unsigned short*>(lf);   // out_bf16 (1 bf16 LF, 2 fp16 HF = y - LF): the same element indices in a 16-bit buffer
-  if (only_if != nullptr && *only_if == 0u) return;      // fallback launch behind the matrix-core kernel: runs only when it raised the flag
+  // fallback launch behind the matrix-core kernel: runs only where that raised the flag -- per problem of a joint call (images
+  // b >= bsplit read word 1), so that one stream's overflow leaves the other stream's matrix-core output in place
+  if (only_if != nullptr && only_if[(int)(blockIdx.x / (unsigned)(nstrip * nseg)) >= bsplit ? 1 : 0] == 0u) return;
   __shared__ V s_a[2][FC][NL];
   __shared__ V s_b[2][FC][NL];
   const int xi = threadIdx.x / NL;
@@ -493,20 +495,20 @@ __global__ __launch_bounds__(FC * NL) void gf_fused_kernel(const float* __restri
 namespace paif_gf2 {
 template <int OM>
 __global__ void gf2_kernel(const float* __restrict__ guide, const float* __restrict__ y, const float* __restrict__ planes, float* __restrict__ lf,
-                           unsigned* __restrict__ flag, int B, int H, int W, int nstrip, int nslots, int rows_per_slot, int total_rows);
+                           unsigned* __restrict__ flag, int B, int H, int W, int nstrip, int nslots, int rows_per_slot, int total_rows, int bsplit);
 extern const int kStripOut, kThreads;      // output columns per strip and threads per workgroup of the build (8 waves: 48, 512; 12 waves: 80, 768)
-extern template __global__ void gf2_kernel<0>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
-extern template __global__ void gf2_kernel<1>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
-extern template __global__ void gf2_kernel<2>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
-extern template __global__ void gf2_kernel<3>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
+extern template __global__ void gf2_kernel<0>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
+extern template __global__ void gf2_kernel<1>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
+extern template __global__ void gf2_kernel<2>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
+extern template __global__ void gf2_kernel<3>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
 }
 namespace paif_gf2w12 {      // gf_mfma2_w12.hip: the 12-wave build, output modes 2 and 3
 template <int OM>
 __global__ void gf2_kernel(const float* __restrict__ guide, const float* __restrict__ y, const float* __restrict__ planes, float* __restrict__ lf,
-                           unsigned* __restrict__ flag, int B, int H, int W, int nstrip, int nslots, int rows_per_slot, int total_rows);
+                           unsigned* __restrict__ flag, int B, int H, int W, int nstrip, int nslots, int rows_per_slot, int total_rows, int bsplit);
 extern const int kStripOut, kThreads;
-extern template __global__ void gf2_kernel<2>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
-extern template __global__ void gf2_kernel<3>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int);
+extern template __global__ void gf2_kernel<2>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
+extern template __global__ void gf2_kernel<3>(const float*, const float*, const float*, float*, unsigned*, int, int, int, int, int, int, int, int);
 }
 
 // The statistics launch alone: the reverse pass (gf_backward.hip) reads the same planes.  workspace: as below.
@@ -524,8 +526,9 @@ extern "C" __attribute__((visibility("hidden"))) int paifi_gf_guide_stats(const 
 extern "C" size_t paif_guided_filter_fused_workspace_floats(int B, int H, int W) { return (size_t)4 * B * H * W + 64; }
 
 static int gf_fused_launch(const float* guide, const float* y, float* lf, float eps0, float eps1, float* workspace, int B, int H, int W,
-                           int out_bf16, paif_stream_t stream) {
+                           int out_bf16, paif_stream_t stream, int bsplit = -1) {
   PAIF_REQUIRE(guide && y && lf && workspace && B > 0, PAIF_EINVAL, "guided_filter_fused: bad arguments");
+  if (bsplit < 0) bsplit = B;     // one problem: every image reports to flag word 0
   PAIF_REQUIRE(H > 2 * R + 1 && W > 2 * R + 1, PAIF_EINVAL, "guided_filter: H,W must exceed 2r+1 = %d (got %dx%d)", K, H, W);
   const int nstrip = (W + FO - 1) / FO;
   // engine: "mfma2" (default; horizontal box sums on the matrix cores, gf_mfma2.hip) or "valu" (the all-VALU kernel below, also the
@@ -563,7 +566,7 @@ static int gf_fused_launch(const float* guide, const float* y, float* lf, float 
     nseg = 1;
     for (int n = 1; n <= 16 && n <= H; ++n) {
       const int rows = (H + n - 1) / n;
-      const long blocks = (long)B * nstrip * n * 2 * zg;
+      const long blocks = (long)bsplit * nstrip * n * 2 * zg;
       const long cost = ((blocks + 256 * res - 1) / (256 * res)) * (rows + warm);
       if (best < 0 || cost < best) { best = cost; nseg = n; }
     }
@@ -583,33 +586,35 @@ static int gf_fused_launch(const float* guide, const float* y, float* lf, float 
     const int grid = (nslots + 7) / 8 * 16;
     if (w12 && out_bf16 == 3)
       hipLaunchKernelGGL((paif_gf2w12::gf2_kernel<3>), dim3(grid), dim3(threads2), 0, st, guide, y, workspace, lf, flag, B, H, W, nstrip2, nslots,
-                         rows_per_slot, (int)total_rows);
+                         rows_per_slot, (int)total_rows, bsplit);
     else if (w12)
       hipLaunchKernelGGL((paif_gf2w12::gf2_kernel<2>), dim3(grid), dim3(threads2), 0, st, guide, y, workspace, lf, flag, B, H, W, nstrip2, nslots,
-                         rows_per_slot, (int)total_rows);
+                         rows_per_slot, (int)total_rows, bsplit);
     else if (out_bf16 == 3)
       hipLaunchKernelGGL((paif_gf2::gf2_kernel<3>), dim3(grid), dim3(threads2), 0, st, guide, y, workspace, lf, flag, B, H, W, nstrip2, nslots,
-                         rows_per_slot, (int)total_rows);
+                         rows_per_slot, (int)total_rows, bsplit);
     else if (out_bf16 == 2)
       hipLaunchKernelGGL((paif_gf2::gf2_kernel<2>), dim3(grid), dim3(threads2), 0, st, guide, y, workspace, lf, flag, B, H, W, nstrip2, nslots,
-                         rows_per_slot, (int)total_rows);
+                         rows_per_slot, (int)total_rows, bsplit);
     else if (out_bf16)
       hipLaunchKernelGGL((paif_gf2::gf2_kernel<1>), dim3(grid), dim3(threads2), 0, st, guide, y, workspace, lf, flag, B, H, W, nstrip2, nslots,
-                         rows_per_slot, (int)total_rows);
+                         rows_per_slot, (int)total_rows, bsplit);
     else
       hipLaunchKernelGGL((paif_gf2::gf2_kernel<0>), dim3(grid), dim3(threads2), 0, st, guide, y, workspace, lf, flag, B, H, W, nstrip2, nslots,
-                         rows_per_slot, (int)total_rows);
+                         rows_per_slot, (int)total_rows, bsplit);
     PAIF_LAUNCH_CHECK("guided_filter_fused(mfma2)");
   }
+  // (the all-VALU kernel sums its row ring in slot order, so its bits depend on where a segment begins: a joint call cuts the images as
+  // the single call of ONE problem does -- pick() counts bsplit images -- and each problem's fallback output is that of its own call)
   int nseg;
   pick(4 * R, resident, zgroups, nseg);
   const int frows = (H + nseg - 1) / nseg;
   const unsigned* only_if = engine == 2 ? flag : nullptr;
   const dim3 grid(B * nstrip * nseg, 2, zgroups);
-  if (form == 0) hipLaunchKernelGGL((gf_fused_kernel<float4, 8>), grid, dim3(FC * 8), 0, st, guide, y, workspace, only_if, lf, B, H, W, nstrip, nseg, frows, out_bf16);
-  else if (form == 1) hipLaunchKernelGGL((gf_fused_kernel<float4, 4>), grid, dim3(FC * 4), 0, st, guide, y, workspace, only_if, lf, B, H, W, nstrip, nseg, frows, out_bf16);
-  else if (form == 2) hipLaunchKernelGGL((gf_fused_kernel<float4, 2>), grid, dim3(FC * 2), 0, st, guide, y, workspace, only_if, lf, B, H, W, nstrip, nseg, frows, out_bf16);
-  else hipLaunchKernelGGL((gf_fused_kernel<float2, 16>), grid, dim3(FC * 16), 0, st, guide, y, workspace, only_if, lf, B, H, W, nstrip, nseg, frows, out_bf16);
+  if (form == 0) hipLaunchKernelGGL((gf_fused_kernel<float4, 8>), grid, dim3(FC * 8), 0, st, guide, y, workspace, only_if, lf, B, H, W, nstrip, nseg, frows, out_bf16, bsplit);
+  else if (form == 1) hipLaunchKernelGGL((gf_fused_kernel<float4, 4>), grid, dim3(FC * 4), 0, st, guide, y, workspace, only_if, lf, B, H, W, nstrip, nseg, frows, out_bf16, bsplit);
+  else if (form == 2) hipLaunchKernelGGL((gf_fused_kernel<float4, 2>), grid, dim3(FC * 2), 0, st, guide, y, workspace, only_if, lf, B, H, W, nstrip, nseg, frows, out_bf16, bsplit);
+  else hipLaunchKernelGGL((gf_fused_kernel<float2, 16>), grid, dim3(FC * 16), 0, st, guide, y, workspace, only_if, lf, B, H, W, nstrip, nseg, frows, out_bf16, bsplit);
   PAIF_LAUNCH_CHECK("guided_filter_fused");
   return 0;
 }
@@ -635,4 +640,24 @@ extern "C" int paif_guided_filter_fused_fwd_hf16_y16(const float* guide, const f
 extern "C" int paif_guided_filter_fused_fwd_bf16(const float* guide, const float* y, float* lf, float eps0, float eps1, float* workspace, int B,
                                                  int H, int W, paif_stream_t stream) {
   return gf_fused_launch(guide, y, lf, eps0, eps1, workspace, B, H, W, 1, stream);
+}
+
+// Two problems of one geometry as ONE batch (the infrared and the visible stream of the fusion forward): images 0 .. bsplit-1 are problem
+// 0, images bsplit .. B-1 problem 1; guide / y / out are the joint [B,..] tensors ([2][B,H,W,32] out).  The kernels carry no weights, so
+// the only per-problem state is the f16-range word: an overflow in one problem sends that problem's images alone through the fallback,
+// and each half holds the bits of its own single call.  out_mode: 0 fp32 LF, 1 bf16 LF, 2 fp16 HF, 3 fp16 HF with y read as fp16.
+// 1 if the matrix-core engine takes the joint batch of B images (its 32-bit offsets, gf_fused_launch); if not, the joint call would run the
+// all-VALU kernel where the two single calls run the matrix-core one: the caller then keeps two single calls.
+extern "C" int paif_guided_filter_fused_joint_fits(int B, int H, int W) {
+  if (B < 2 || H <= 2 * R + 1 || W <= 2 * R + 1) return 0;
+  const int so = paif_gf2::kStripOut < paif_gf2w12::kStripOut ? paif_gf2::kStripOut : paif_gf2w12::kStripOut;
+  const size_t ns = (size_t)(W + so - 1) / so;
+  return ((size_t)(B + 1) * H * W * 128 < 0x7FF00000ull && (size_t)B * ns * H < 0x7FFFFFFFull) ? 1 : 0;
+}
+
+extern "C" int paif_guided_filter_fused_fwd_joint(const float* guide, const float* y, float* out, float eps0, float eps1, float* workspace,
+                                                  int B, int bsplit, int H, int W, int out_mode, paif_stream_t stream) {
+  PAIF_REQUIRE(out_mode >= 0 && out_mode <= 3 && bsplit > 0 && B == 2 * bsplit, PAIF_EINVAL,
+               "guided_filter_fused_joint: out_mode %d / bsplit %d of %d images (two problems of bsplit images each)", out_mode, bsplit, B);
+  return gf_fused_launch(guide, y, out, eps0, eps1, workspace, B, H, W, out_mode, stream, bsplit);
 }

@@ -248,6 +248,17 @@ class ResidualDenseBlock(_HipOp):
         tape.append(dict(x1=x1, x2=x2, z3=z3))
         return out
 
+    @staticmethod
+    def forward_pair_nhwc(b0, x0, b1, x1):
+        """b0.forward_nhwc(x0), b1.forward_nhwc(x1) of two blocks with k = 3, d = 1 on maps of one shape (inference, 16-bit maps, no further
+        residual maps, no ChannelPool): each of the three convs as one pair launch where ops.conv2d_pair has the form."""
+        k0 = dict(kh=3, dil=1, act=ops.ACT_PRELU, prelu=b0.lrelu.weight)
+        k1 = dict(kh=3, dil=1, act=ops.ACT_PRELU, prelu=b1.lrelu.weight)
+        y0, y1 = ops.conv2d_pair(dict(srcs=[x0], wpk=b0.conv1.wpk(1, 32), **k0), dict(srcs=[x1], wpk=b1.conv1.wpk(1, 32), **k1))
+        z0, z1 = ops.conv2d_pair(dict(srcs=[x0, y0], wpk=b0.conv2.wpk(2, 32), **k0), dict(srcs=[x1, y1], wpk=b1.conv2.wpk(2, 32), **k1))
+        return ops.conv2d_pair(dict(srcs=[x0, y0, z0], wpk=b0.conv3.wpk(3, 32), alpha=0.333333, res=(x0,), **k0),
+                               dict(srcs=[x1, y1, z1], wpk=b1.conv3.wpk(3, 32), alpha=0.333333, res=(x1,), **k1))
+
     bwd_takes_res = True    # backward_nhwc(..., res=(m,)): m is added to the returned gradient in the last dgrad conv's epilogue
 
     def backward_nhwc(self, g, t, wgrad=False, res=()):

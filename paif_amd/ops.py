@@ -79,6 +79,9 @@ CONFIG = {"conv_precision": "bf16x3", "gemm_precision": _env_gemm_precision(), "
           # inference forward of the fusion network: run the infrared and the visible stream on two HIP streams (identical results; off by
           # default because per-launch timings -- bench.py's roofline blocks, rocprofv3 averages -- then measure CU sharing, not kernels)
           "two_stream": False,
+          # inference forward, 16-bit storage, single-stream mode: the two streams' stems run as ONE launch (stem_pair) and their guided
+          # filters as one joint batch of 2B images (guided_filter_pair(bsplit=B)) -- identical bits, fewer launches; False = two launches each
+          "stream_pair": True,
           # round 5: ChannelPool(ir_feature, vis_feature) from the producing convs' epilogues (paif_conv_desc.cpool) instead of a pass of its own;
           # fp16 storage: the forward's last 32-channel map as fp32 / the folded 1x1 with fp16 hi + lo weights (ablation switches)
           "cpool_fused": True, "f16_last_f32": True, "f16_decomp_split": False,
@@ -633,16 +636,22 @@ def u8_to_i64(src):
 # ---------------------------------------------------------------------------------------------
 # fusion network pieces (all NHWC)
 # ---------------------------------------------------------------------------------------------
+def _plane_view(img):
+    """-> (img with dense planes, its batch stride in floats) for the stem kernels."""
+    B, _, H, W = img.shape
+    if img.dtype != torch.float32 or not img.is_cuda:
+        raise RuntimeError("stem: need a float32 CUDA tensor")
+    if img.stride(3) != 1 or img.stride(2) != W:
+        img = img.contiguous()
+    return img, (img.stride(0) if B > 1 else H * W)
+
+
 def stem(img, w, prelu, want_guide=True):
     """img: [B,1,H,W] or a channel-0 view of [B,C,H,W] (dense planes, arbitrary batch stride)."""
     B, _, H, W = img.shape
-    if img.stride(3) != 1 or img.stride(2) != W:
-        img = img.contiguous()
-    bstride = img.stride(0) if B > 1 else H * W
+    img, bstride = _plane_view(img)
     feat = None if (_ACT_BF16[0] is torch.float16 and CONFIG["gf_in_f16"]) else torch.empty((B, H, W, 32), device=img.device, dtype=torch.float32)
     guide = torch.empty((B, H, W), device=img.device, dtype=torch.float32) if want_guide else None
-    if img.dtype != torch.float32 or not img.is_cuda:
-        raise RuntimeError("stem: need a float32 CUDA tensor")
     if _ACT_BF16[0] is torch.float16 and CONFIG["gf_in_f16"]:
         # fp16 storage, round 6: the stem writes its map as fp16 ONLY (the guide still comes from the fp32 values); the guided filter reads
         # that map (HF = x16 - LF(x16), the x16 the folded 1x1 takes as its first source anyway) -- no fp32 stem map exists in this forward
@@ -662,6 +671,42 @@ def stem(img, w, prelu, want_guide=True):
     return feat, guide
 
 
+def pair_halves(joint, B):
+    """The two problems' halves of a joint [2B,...] tensor of a pair launch: dense views (problem 0 = images 0..B-1)."""
+    return joint[:B], joint[B:]
+
+
+def register_twin_halves(feat, twin, B):
+    """_TWINS is keyed by data_ptr and checked by identity: the two half-views of a joint fp32 map must each find their half of the
+    joint 16-bit twin (cast_storage).  -> the two registered half-views of feat."""
+    halves = pair_halves(feat, B)
+    for h, t in zip(halves, pair_halves(twin, B)):
+        _TWINS[h.data_ptr()] = (h, t)
+    return halves
+
+
+def stem_pair(img0, w0, prelu0, img1, w1, prelu1):
+    """stem(img0, w0, prelu0) and stem(img1, w1, prelu1) of one geometry as ONE launch.  -> (feat [2B,H,W,32], guide [2B,H,W], (f0, f1)):
+    the joint map (fp32; the fp16 twin alone under CONFIG["gf_in_f16"]) and guide, problem p in images p*B .. p*B + B - 1, and the map's
+    two half-views (registered with their 16-bit twins' halves in a 16-bit storage forward).  Bits of two stem() calls."""
+    if img0.shape != img1.shape:
+        raise ValueError("stem_pair: the two images differ in shape: %s / %s" % (tuple(img0.shape), tuple(img1.shape)))
+    B, _, H, W = img0.shape
+    img0, bs0 = _plane_view(img0)
+    img1, bs1 = _plane_view(img1)
+    dev, st = img0.device, _ACT_BF16[0]
+    only16 = st is torch.float16 and CONFIG["gf_in_f16"]
+    feat = None if only16 else torch.empty((2 * B, H, W, 32), device=dev, dtype=torch.float32)
+    twin = torch.empty((2 * B, H, W, 32), device=dev, dtype=st) if st else None
+    guide = torch.empty((2 * B, H, W), device=dev, dtype=torch.float32)
+    _lib.check(lib().paif_stem_fwd_pair(ctypes.c_void_p(img0.data_ptr()), bs0, _p(w0), _p(prelu0), ctypes.c_void_p(img1.data_ptr()), bs1,
+                                        _p(w1), _p(prelu1), _p(feat), _pa(twin), 0 if twin is None else 2 if st is torch.float16 else 1,
+                                        _p(guide), B, H, W, _stream()), "stem_pair")
+    if only16:
+        return twin, guide, pair_halves(twin, B)
+    return feat, guide, (register_twin_halves(feat, twin, B) if twin is not None else pair_halves(feat, B))
+
+
 def channel_residue(x):
     B, H, W, C = x.shape
     assert C == 32
@@ -679,12 +724,20 @@ class GfTape:
         self.mc, self.stats = mc, stats
 
 
-def guided_filter_pair(guide, y, eps=(0.001, 0.0001), want_ab=False, out_bf16=False, tape=None):
+def guided_filter_joint_fits(B2, H, W):
+    """True if guided_filter_pair(bsplit=...) takes a joint batch of B2 images on the engine the single calls run on."""
+    return H > 9 and W > 9 and bool(lib().paif_guided_filter_fused_joint_fits(B2, H, W))
+
+
+def guided_filter_pair(guide, y, eps=(0.001, 0.0001), want_ab=False, out_bf16=False, tape=None, bsplit=None):
     """Returns lf [2,B,H,W,32] for the two eps (r = 4) (and the coefficient maps ab [4,B,H,W,32] for the
     backward pass).  AssertionError if H or W <= 9, like the reference's guided_filter_pytorch.
     out_bf16 (inference, fused form): the two maps as bf16 -- the bf16 configuration's storage of the maps behind this block;
     out_bf16 = torch.float16 (the fp16 configuration): the two HIGH-frequency maps y - LF as fp16 instead (paif_hip.h
-    paif_guided_filter_fused_fwd_hf16)."""
+    paif_guided_filter_fused_fwd_hf16).
+    bsplit (inference, fused form): guide / y are the JOINT tensors of two problems of one geometry (images 0..bsplit-1 and bsplit..B-1,
+    the two streams of the fusion forward): one launch sequence for both, the f16-range fallback decided per problem -- each half of
+    lf[e] holds the bits of its own call (one qualification: include/paif_hip.h)."""
     hf16 = out_bf16 is torch.float16
     out_bf16 = bool(out_bf16)
     B, H, W, C = y.shape
@@ -703,11 +756,16 @@ def guided_filter_pair(guide, y, eps=(0.001, 0.0001), want_ab=False, out_bf16=Fa
             raise NotImplementedError("guided filter: an fp16 target map is built for the fp16 configuration's high-frequency output only")
         fn = (L.paif_guided_filter_fused_fwd_hf16_y16 if y16 else L.paif_guided_filter_fused_fwd_hf16 if hf16 else
               L.paif_guided_filter_fused_fwd_bf16 if out_bf16 else L.paif_guided_filter_fused_fwd)
-        _lib.check(fn(_p(guide), _pa(y) if y16 else _p(y), _pa(lf), eps[0], eps[1], _p(ws), B, H, W, _stream()), "guided_filter_fused")
+        if bsplit is not None:
+            _lib.check(L.paif_guided_filter_fused_fwd_joint(_p(guide), _pa(y) if y16 else _p(y), _pa(lf), eps[0], eps[1], _p(ws), B, bsplit, H, W,
+                                                            3 if y16 else 2 if hf16 else 1 if out_bf16 else 0, _stream()), "guided_filter_fused")
+        else:
+            _lib.check(fn(_p(guide), _pa(y) if y16 else _p(y), _pa(lf), eps[0], eps[1], _p(ws), B, H, W, _stream()), "guided_filter_fused")
         if e0 is not None:   # algorithmic traffic: guide + y read once, the two low-frequency maps written once; ~650 FLOP per pixel-channel
             TIMER.stop(tag, e0, 650 * B * H * W * 32, B * H * W * (4 + (2 if y16 else 4) * 32 + (2 if out_bf16 else 4) * 64))
         return lf
     assert not out_bf16, "bf16 low-frequency maps are an inference (fused-form) output"
+    assert bsplit is None, "the joint batch of two problems is an inference (fused-form) call"
     lf = torch.empty((2, B, H, W, 32), device=y.device, dtype=torch.float32)
     import os
     # tape: "mc" / "ab" force the round-6 streaming pair / the round-1 pair (tests, A/B runs); default: streaming wherever it fits
@@ -866,9 +924,50 @@ def conv2d_kernel_name(desc, B, H, W):
     return buf.value.decode()
 
 
+def _launch_convs(pend):
+    """Launch prepared conv descriptors [(desc, (B, H, W), (flops, bytes, residual bytes), keep-alive)]: two of one shape as ONE pair launch
+    where paif_conv2d_fwd_pair has the form (and CONFIG["stream_pair"] is on), else one launch each.  KernelTimer: one start / stop per
+    launch, a pair launch with the work of both problems."""
+    L = lib()
+    if len(pend) == 2 and pend[0][1] == pend[1][1] and CONFIG.get("stream_pair", True):
+        (d0, (B, H, W), w0, _), (d1, _, w1, _) = pend
+        buf = ctypes.create_string_buffer(96)
+        if L.paif_conv2d_pair_kernel_name(ctypes.byref(d0), ctypes.byref(d1), B, H, W, buf, len(buf)) == 0:
+            tag = buf.value.decode()
+            e0 = TIMER.start(tag) if TIMER is not None else None
+            _lib.check(L.paif_conv2d_fwd_pair(ctypes.byref(d0), ctypes.byref(d1), B, H, W, _stream()), "conv2d_pair")
+            if e0 is not None:
+                TIMER.stop(tag, e0, w0[0] + w1[0], w0[1] + w1[1], w0[2] + w1[2])
+            return True
+    for d, (B, H, W), work, _ in pend:
+        e0 = None
+        if TIMER is not None:   # name the kernel this launch takes, as rocprofv3 will list it
+            tag = conv2d_kernel_name(d, B, H, W)
+            e0 = TIMER.start(tag)
+        _lib.check(L.paif_conv2d_fwd(ctypes.byref(d), B, H, W, _stream()), "conv2d")
+        if e0 is not None:
+            TIMER.stop(tag, e0, *work)
+    return False
+
+
+def conv2d_pair(kw0, kw1):
+    """conv2d(**kw0) and conv2d(**kw1) -- two problems of one geometry, e.g. the same layer of the two image streams -- as ONE launch where
+    the pair form exists (paif_conv2d_fwd_pair: the LDS-DMA 1x1, the LDS-DMA 3x3 tile kernel for 1, 2 sources or 3 sources + 1
+    residual map); otherwise as the two single launches.  Same bits either way.  -> (out0, out1)."""
+    pend = []
+    o0 = conv2d(_defer=pend, **kw0)
+    n0 = len(pend)
+    o1 = conv2d(_defer=pend, **kw1)
+    if n0 == 1 and len(pend) == 2:
+        _launch_convs(pend)
+    elif pend:          # one of the two was launched by conv2d itself (a request the pair form has not): the other one alone
+        _launch_convs(pend)
+    return o0, o1
+
+
 def conv2d(srcs, wpk, kh, dil=1, cin=32, cout=32, in_act=ACT_NONE, in_prelu=None, scale=None, shift=None,
            act=ACT_NONE, prelu=None, alpha=1.0, res=(), pool=False, want_aux=False, in_aux=None, in_scale=None,
-           in_alpha=1.0, epi_dact=0, epi_aux=None, out=None, out_f32=False, cpool=None):
+           in_alpha=1.0, epi_dact=0, epi_aux=None, out=None, out_f32=False, cpool=None, _defer=None):
     """Dense conv over the virtual concat of `srcs` (NHWC).  Returns out (and the per-tile pool partials /
     the saved pre-activation when asked).  in_act 3/4/5 + in_aux/in_scale/in_alpha and epi_dact/epi_aux are the
     activation-derivative hooks used when the same kernel runs a dgrad (include/paif_hip.h).
@@ -951,17 +1050,16 @@ def conv2d(srcs, wpk, kh, dil=1, cin=32, cout=32, in_act=ACT_NONE, in_prelu=None
     if CONFIG.get("serpentine", True):     # consecutive dense-conv launches walk their tiles in opposite directions (paif_hip.h)
         _SERP[0] ^= 1
         d.reverse_tiles = _SERP[0]
-    e0 = None
-    if TIMER is not None:   # name the kernel this launch takes, as rocprofv3 will list it
-        tag = conv2d_kernel_name(d, B, H, W)
-        e0 = TIMER.start(tag)
-    _lib.check(L.paif_conv2d_fwd(ctypes.byref(d), B, H, W, _stream()), "conv2d")
-    if e0 is not None:
-        px = B * H * W
-        # algorithmic work: 2*K*cout FLOP per output pixel; each source map read once, output written once
-        eb_in, eb_out = (2 if src_bf else 4), (2 if out_bf else 4)
-        eb_res = 2 if (res and res[0].dtype in H16) else 4
-        TIMER.stop(tag, e0, 2 * px * kh * kh * cin * len(srcs) * cout, px * (eb_in * cin * len(srcs) + eb_out * cout), px * eb_res * cout * len(res))
+    px = B * H * W
+    # algorithmic work: 2*K*cout FLOP per output pixel; each source map read once, output written once
+    eb_in, eb_out = (2 if src_bf else 4), (2 if out_bf else 4)
+    eb_res = 2 if (res and res[0].dtype in H16) else 4
+    work = (2 * px * kh * kh * cin * len(srcs) * cout, px * (eb_in * cin * len(srcs) + eb_out * cout), px * eb_res * cout * len(res))
+    if _defer is not None and not extra and pool_after is None and not pool and not want_aux:
+        # conv2d_pair: the descriptor is complete, the launch is the caller's (the tensors it points into travel with it)
+        _defer.append((d, (B, H, W), work, (srcs, res, out, wpk, scale, shift, prelu, in_prelu)))
+        return out
+    _launch_convs([(d, (B, H, W), work, None)])
     for r in extra:  # more than 3 fused residuals: plain adds
         out = add(out, r)
     if pool_after is not None:
