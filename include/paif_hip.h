@@ -970,6 +970,69 @@ int paif_didfuse_conv_bwd(const float* pack, int layer, float slope, const float
 int paif_didfuse_stem_bwd(const float* pack, int stream_id, float slope, const float* enc, const float* dg, const float* d_d2, float* d_x,
                           int B, int H, int W, paif_stream_t stream);
 
+/* BFFusion baseline (fusion_model/BFFusion.py of the reference, class BFFR; csrc/bffusion.hip, csrc/conv_slab.h).  fp32 throughout, NHWC
+ * maps at a pixel stride `*_cs` in floats; a pointer names the first channel of the slice a launch works on.  The module's table
+ * (paif_amd/ops.py: bffusion_forward / bffusion_backward) strings these launches together.  No atomics, no host synchronisation, no
+ * allocation: capturable and bit-reproducible.  B H W < 2^26. */
+/* Floats of the operand pack of a conv with M output and K input channels (both padded to 16), taps = 1 or 9; 0 for bad arguments. */
+size_t paif_bffusion_ops_floats(int M, int K, int taps);
+/* One weight [co][n][taps] into a ZEROED operand pack, its n input channels at [off, off + n) of the conv's concat (several weights side
+ * by side fill one pack).  transposed = 0: M = co, K = concat; 1: M = concat, K = co, taps flipped. */
+int paif_bffusion_pack_ops(const float* w, int co, int n, int off, int M, int K, int taps, int transposed, float* dst, paif_stream_t stream);
+/* A slab conv on v_mfma_f32_16x16x4_f32: K channels of `in` -> M channels of `out`.  epi: 0 LeakyReLU(. + bias, slope) (slope 0: ReLU,
+ * slope 1: the identity), 1 store, 2 add to `out`.  mask (or null): the taped map behind `in`, same stride; the staged value is
+ * LeakyReLU'(mask) in.  refl: 0 zero padding; 1 reflected staging (forward); 2 the transposed half, `out` is a RING map
+ * [B][H + 2][W + 2][out_cs] for paif_bffusion_fold.  Forms: (taps, refl, mask, epi) = (9,0,-,0) (9,1,-,0) (1,0,-,0) (1,0,-,1) (1,0,m,1)
+ * (9,0,m,2) (9,2,m,1). */
+int paif_bffusion_conv(const float* wpk, const float* bias, float slope, int epi, int taps, int refl, const float* in, const float* mask,
+                       int in_cs, int K, float* out, int out_cs, int M, int B, int H, int W, paif_stream_t stream);
+/* ring [B][H + 2][W + 2][M] -> dst: pixel (y, x) takes ring (y + 1, x + 1), row 1 also ring row 0, row H - 2 also ring row H + 1, columns
+ * alike.  Channels below n_store are written, the others added to. */
+int paif_bffusion_fold(const float* ring, int M, int n_store, float* dst, int dst_cs, int B, int H, int W, paif_stream_t stream);
+/* 1 x 1 conv 1 -> 16 with bias, no activation, of plane b at x + b * sb -> channels [0, 16) of out; its transpose -> d_x [B,H,W]. */
+int paif_bffusion_stem_fwd(const float* x, size_t sb, const float* w, const float* bias, float* out, int out_cs, int B, int H, int W,
+                           paif_stream_t stream);
+int paif_bffusion_stem_bwd(const float* w, const float* d, int d_cs, float* d_x, int B, int H, int W, paif_stream_t stream);
+/* fused = tanh(1 x 1 conv 16 -> 1 + bias) / 2 + 0.5; the reverse takes the derivative off the taped plane and WRITES 16 channels of d. */
+int paif_bffusion_head_fwd(const float* w, const float* bias, const float* in, int in_cs, float* fused, int B, int H, int W,
+                           paif_stream_t stream);
+int paif_bffusion_head_bwd(const float* w, const float* fused, const float* d_fused, float* d, int d_cs, int B, int H, int W,
+                           paif_stream_t stream);
+/* MaxPool2d(2, 2) of an H x W map -> (H / 2) x (W / 2).  The reverse reads the choice off the taped pre-pool map (the first maximum in
+ * row-major window order) and ADDS to d_in; dropped rows and columns get nothing. */
+int paif_bffusion_pool_fwd(const float* in, int in_cs, int C, float* out, int out_cs, int B, int H, int W, paif_stream_t stream);
+int paif_bffusion_pool_bwd(const float* in, int in_cs, int C, const float* d_pooled, int dp_cs, float* d_in, int din_cs, int B, int H, int W,
+                           paif_stream_t stream);
+/* Nearest x 2 of an (H / 2) x (W / 2) map into an H x W slab slice, an odd last row / column reflected (= the last source row / column).
+ * The reverse sums every source pixel's readers in a fixed order and writes (add = 0) or adds to (1) d_src. */
+int paif_bffusion_up_fwd(const float* src, int src_cs, int C, float* dst, int dst_cs, int B, int H, int W, paif_stream_t stream);
+int paif_bffusion_up_bwd(const float* d_dst, int dd_cs, int C, float* d_src, int ds_cs, int add, int B, int H, int W, paif_stream_t stream);
+/* out = 0.5 ((skip_a + skip_a x_a) + (skip_b + skip_b x_b)); x_*: dense [.., C].  Reverse of one block: d_x = 0.5 skip d_fused,
+ * d_skip = 0.5 d_fused (1 + x), both dense and WRITTEN. */
+int paif_bffusion_gate_fwd(const float* skip_a, int sa_cs, const float* x_a, const float* skip_b, int sb_cs, const float* x_b, int C, float* out,
+                           int out_cs, int B, int H, int W, paif_stream_t stream);
+int paif_bffusion_gate_bwd(const float* d_fused, int df_cs, const float* skip, int skip_cs, const float* x, int C, float* d_x, float* d_skip,
+                           int B, int H, int W, paif_stream_t stream);
+/* LayerNorm over the C channels of every pixel of a dense map; the reverse reads the taped INPUT y. */
+int paif_bffusion_ln_fwd(const float* y, const float* gamma, const float* beta, float eps, int C, float* z, int B, int H, int W,
+                         paif_stream_t stream);
+int paif_bffusion_ln_bwd(const float* y, const float* gamma, float eps, int C, const float* d_z, float* d_y, int B, int H, int W,
+                         paif_stream_t stream);
+/* The channel attention.  Chunks of the two-stage reduction over the H W pixels of an image (a function of H W alone). */
+int paif_bffusion_ctx_chunks(int H, int W);
+/* partial [B][chunks][dim d] (float64): per chunk, sum over pixels of a[n][c] b[n][(c / d) d + j] for c < dim, j < d. */
+int paif_bffusion_ctx_partial(const float* a, int a_cs, const float* b, int b_cs, int dim, int d, double* partial, int B, int H, int W,
+                              paif_stream_t stream);
+/* ctx [B][dim][d] = softmax over i (within a head) of scale * the sum of the chunks; the reverse turns the chunks of d_ctx into the
+ * cotangent d_s of q^T k. */
+int paif_bffusion_ctx_softmax(const double* partial, int dim, int d, float scale, float* ctx, int B, int H, int W, paif_stream_t stream);
+int paif_bffusion_ctx_softmax_bwd(const double* partial, int dim, int d, float scale, const float* ctx, float* d_s, int B, int H, int W,
+                                  paif_stream_t stream);
+/* x = v ctx per pixel and head (qkv: dense [.., 3 dim] = q | k | v); the reverse writes d_qkv from d_x, ctx and d_s. */
+int paif_bffusion_attn_apply_fwd(const float* qkv, const float* ctx, int dim, int d, float* x, int B, int H, int W, paif_stream_t stream);
+int paif_bffusion_attn_apply_bwd(const float* qkv, const float* d_x, const float* ctx, const float* d_s, int dim, int d, float* d_qkv, int B,
+                                 int H, int W, paif_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -250,6 +250,28 @@ SIGNATURES = {
     "paif_didfuse_head_bwd": (c_int, [F, F, F, F, c_int, c_int, c_int, F]),
     "paif_didfuse_conv_bwd": (c_int, [F, c_int, c_float, F, F, F, F, c_int, c_int, c_int, F]),
     "paif_didfuse_stem_bwd": (c_int, [F, c_int, c_float, F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_ops_floats": (c_size_t, [c_int, c_int, c_int]),
+    "paif_bffusion_pack_ops": (c_int, [F, c_int, c_int, c_int, c_int, c_int, c_int, c_int, F, F]),
+    "paif_bffusion_conv": (c_int, [F, F, c_float, c_int, c_int, c_int, F, F, c_int, c_int, F, c_int, c_int, c_int, c_int, c_int, F]),
+    "paif_bffusion_fold": (c_int, [F, c_int, c_int, F, c_int, c_int, c_int, c_int, F]),
+    "paif_bffusion_stem_fwd": (c_int, [F, c_size_t, F, F, F, c_int, c_int, c_int, c_int, F]),
+    "paif_bffusion_stem_bwd": (c_int, [F, F, c_int, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_head_fwd": (c_int, [F, F, F, c_int, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_head_bwd": (c_int, [F, F, F, F, c_int, c_int, c_int, c_int, F]),
+    "paif_bffusion_pool_fwd": (c_int, [F, c_int, c_int, F, c_int, c_int, c_int, c_int, F]),
+    "paif_bffusion_pool_bwd": (c_int, [F, c_int, c_int, F, c_int, F, c_int, c_int, c_int, c_int, F]),
+    "paif_bffusion_up_fwd": (c_int, [F, c_int, c_int, F, c_int, c_int, c_int, c_int, F]),
+    "paif_bffusion_up_bwd": (c_int, [F, c_int, c_int, F, c_int, c_int, c_int, c_int, c_int, F]),
+    "paif_bffusion_gate_fwd": (c_int, [F, c_int, F, F, c_int, F, c_int, F, c_int, c_int, c_int, c_int, F]),
+    "paif_bffusion_gate_bwd": (c_int, [F, c_int, F, c_int, F, c_int, F, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_ln_fwd": (c_int, [F, F, F, c_float, c_int, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_ln_bwd": (c_int, [F, F, c_float, c_int, F, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_ctx_chunks": (c_int, [c_int, c_int]),
+    "paif_bffusion_ctx_partial": (c_int, [F, c_int, F, c_int, c_int, c_int, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_ctx_softmax": (c_int, [F, c_int, c_int, c_float, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_ctx_softmax_bwd": (c_int, [F, c_int, c_int, c_float, F, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_attn_apply_fwd": (c_int, [F, F, c_int, c_int, F, c_int, c_int, c_int, F]),
+    "paif_bffusion_attn_apply_bwd": (c_int, [F, F, F, F, c_int, c_int, F, c_int, c_int, c_int, F]),
 }
 
 _lib = None

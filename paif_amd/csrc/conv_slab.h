@@ -6,8 +6,12 @@
 //   * EPI_ACT adds up to two biases (a 1 x 1 over two weight matrices side by side sums both convs' biases);
 //   * ACT: the activation of the store epilogue and of the input mask is LeakyReLU (the default) or tanh (mask 1 - taped^2);
 //   * PAIR: the epilogue also reads the quad another map holds at the same place and stores the mean of the two into a third map;
-//   * XIN: the masked staging scales its input (1), and adds a scaled second input before the mask (2); the mask has its own stride.
-// The last three default to what the header did before them: an instantiation that does not name them compiles to the same code.
+//   * XIN: the masked staging scales its input (1), and adds a scaled second input before the mask (2); the mask has its own stride;
+//   * REFL: REFL_STAGE stages the halo by REFLECTION (row -1 takes row 1, row H takes row H - 2: ReflectionPad2d(1) in front of the conv);
+//     REFL_RING is the transpose's half of that: the zero-pad conv evaluated on the (H + 2) x (W + 2) grid, the input read one pixel up
+//     and left, the output a ring map [B][H + 2][W + 2][out_cs] that a fold pass adds back onto the plane (bffusion.hip: fold_k).
+//   ReLU is LeakyReLU at slope 0, epilogue and mask alike (a negative input stores -0, which every consumer treats as 0).
+// The last four default to what the header did before them: an instantiation that does not name them compiles to the same code.
 // Everything else is conv_k's.  Output CHANNELS on M, 16 PIXELS of one image row on N; the D operand of lane l is channels
 // 4 (l >> 4) .. + 3 of pixel l & 15, one float4 of the NHWC map, and the B operand of four consecutive instructions is one float4 of the
 // input map.  A workgroup of four waves owns a 16 x 16 pixel tile (four rows per wave) and MB blocks of 16 output channels (blockIdx.y
@@ -28,6 +32,7 @@ constexpr int DT = 16;   // tile edge: 4 waves x 4 rows of 16 pixels
 enum { EPI_ACT = 0, EPI_STORE = 1, EPI_ADD = 2 };
 enum { ACT_LEAKY = 0, ACT_TANH = 1 };
 enum { XIN_PLAIN = 0, XIN_SCALED = 1, XIN_SUM = 2 };
+enum { REFL_NONE = 0, REFL_STAGE = 1, REFL_RING = 2 };
 
 // One operand pack: M output channels in `groups` groups of MB blocks of 16, K input channels in `chunks` chunks of 16, `taps` taps.
 struct Plan {
@@ -64,6 +69,9 @@ static __global__ void pack_ops_k(const float* __restrict__ w, int co, int n, in
   }
 }
 
+// reflection padding by one: the row a read at y takes (y in [-1, H]; H >= 2)
+__device__ __forceinline__ int refl1(int y, int H) { return y < 0 ? -y : (y >= H ? 2 * H - 2 - y : y); }
+
 __device__ __forceinline__ float leaky(float v, float s) { return v > 0.f ? v : s * v; }
 // the branch is read off the taped OUTPUT (same sign as the pre-activation; exactly 0 takes the slope, as torch)
 __device__ __forceinline__ float dleaky(float out, float g, float s) { return out > 0.f ? g : s * g; }
@@ -99,20 +107,23 @@ struct ConvArgs {
   int mask_cs = 0;
 };
 
-template <int TAPS, int MB, bool MASK, int EPI, int ACT = ACT_LEAKY, bool PAIR = false, int XIN = XIN_PLAIN>
+template <int TAPS, int MB, bool MASK, int EPI, int ACT = ACT_LEAKY, bool PAIR = false, int XIN = XIN_PLAIN, int REFL = REFL_NONE>
 __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
   static_assert(TAPS == 9 || TAPS == 1, "3 x 3 or 1 x 1");
   static_assert(!PAIR || EPI == EPI_ACT, "the pair store belongs to the activation epilogue");
   static_assert(XIN == XIN_PLAIN || MASK, "the extended staging is the masked one");
+  static_assert(REFL == REFL_NONE || (TAPS == 9 && !PAIR && XIN == XIN_PLAIN), "reflection belongs to the plain 3 x 3 forms");
   constexpr int HALO = TAPS == 9 ? 1 : 0, DP = DT + 2 * HALO;
   constexpr int QS = (DP * DP + 15) / 16 * 16;   // quad stride in float4, a multiple of 256 B: quad planes start at the same LDS bank
   __shared__ float4 s_x[4 * QS];
   __shared__ float4 s_w[TAPS * MB * 64];
   const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, q = lane >> 4, p = lane & 15;
-  const int H = a.H, W = a.W;
+  const int H = a.H, W = a.W;                                                          // the INPUT plane
+  constexpr int RING = REFL == REFL_RING ? 1 : 0;
+  const int Ho = H + 2 * RING, Wo = W + 2 * RING;                                       // the output grid (tx, ty tile it)
   const int b = blockIdx.x / (a.tx * a.ty), rem = blockIdx.x - b * a.tx * a.ty, by = rem / a.tx, bx = rem - by * a.tx;
   const int y0 = by * DT, x0 = bx * DT, r0 = 4 * wave;
-  const size_t img = (size_t)b * H * W;
+  const size_t img = (size_t)b * H * W, imgo = RING ? (size_t)b * Ho * Wo : img;
   const float4* __restrict__ wg = reinterpret_cast<const float4*>(a.wpk) + (size_t)blockIdx.y * a.chunks * (TAPS * MB * 64);
 
   f32x4 acc[MB][4];
@@ -124,7 +135,9 @@ __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
   for (int c = 0; c < a.chunks; ++c) {
     if (c) __syncthreads();   // the previous chunk has been read
     for (int e = tid; e < DP * DP * 4; e += 256) {
-      const int sq = e & 3, pix = e >> 2, ly = pix / DP, lx = pix - ly * DP, gy = y0 - HALO + ly, gx = x0 - HALO + lx, gq = 4 * c + sq;
+      const int sq = e & 3, pix = e >> 2, ly = pix / DP, lx = pix - ly * DP, gq = 4 * c + sq;
+      int gy = y0 - HALO - RING + ly, gx = x0 - HALO - RING + lx;
+      if constexpr (REFL == REFL_STAGE) gy = refl1(gy, H), gx = refl1(gx, W);   // rows past H + 1 may leave the plane again: zero
       float4 v = make_float4(0.f, 0.f, 0.f, 0.f);
       if ((unsigned)gy < (unsigned)H && (unsigned)gx < (unsigned)W && gq < a.nq) {
         const size_t o = (img + (size_t)gy * W + gx) * a.in_cs + 4 * gq;
@@ -169,7 +182,7 @@ __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
   }
 
   const int gx = x0 + p;
-  if (gx >= W) return;
+  if (gx >= Wo) return;
 #pragma unroll
   for (int mb = 0; mb < MB; ++mb) {
     const int co = 16 * ((int)blockIdx.y * MB + mb) + 4 * q;   // out_n is a multiple of 4: a quad is written whole or not at all
@@ -185,8 +198,8 @@ __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
 #pragma unroll
     for (int r = 0; r < 4; ++r) {
       const int gy = y0 + r0 + r;
-      if (gy >= H) continue;
-      const size_t px = img + (size_t)gy * W + gx;
+      if (gy >= Ho) continue;
+      const size_t px = imgo + (size_t)gy * Wo + gx;
       float4* o = reinterpret_cast<float4*>(a.out + px * a.out_cs + a.out_off + co);   // owned by this lane
       const f32x4 v = acc[mb][r];
       if constexpr (EPI == EPI_ACT) {
@@ -214,6 +227,14 @@ void launch_conv(int MB, dim3 grid, hipStream_t s, const ConvArgs& a) {
   else if (MB == 3) hipLaunchKernelGGL((conv_k<TAPS, 3, MASK, EPI>), grid, dim3(256), 0, s, a);
   else if (MB == 2) hipLaunchKernelGGL((conv_k<TAPS, 2, MASK, EPI>), grid, dim3(256), 0, s, a);
   else hipLaunchKernelGGL((conv_k<TAPS, 1, MASK, EPI>), grid, dim3(256), 0, s, a);
+}
+// the 3 x 3 forms with reflection: REFL_STAGE (forward) or REFL_RING (transposed, onto the ring map)
+template <bool MASK, int EPI, int REFL>
+void launch_conv_r(int MB, dim3 grid, hipStream_t s, const ConvArgs& a) {
+  if (MB == 4) hipLaunchKernelGGL((conv_k<9, 4, MASK, EPI, ACT_LEAKY, false, XIN_PLAIN, REFL>), grid, dim3(256), 0, s, a);
+  else if (MB == 3) hipLaunchKernelGGL((conv_k<9, 3, MASK, EPI, ACT_LEAKY, false, XIN_PLAIN, REFL>), grid, dim3(256), 0, s, a);
+  else if (MB == 2) hipLaunchKernelGGL((conv_k<9, 2, MASK, EPI, ACT_LEAKY, false, XIN_PLAIN, REFL>), grid, dim3(256), 0, s, a);
+  else hipLaunchKernelGGL((conv_k<9, 1, MASK, EPI, ACT_LEAKY, false, XIN_PLAIN, REFL>), grid, dim3(256), 0, s, a);
 }
 // the 3 x 3, MB = 4 form with the later template parameters named
 template <bool MASK, int EPI, int ACT, bool PAIR, int XIN>

@@ -2580,3 +2580,255 @@ def didfuse_backward(maps, fused, d_fused, pack):
         _lib.check(L.paif_didfuse_stem_bwd(wp, s, sl[2 * s], e, _p(dg), _p(d_d2), _p(d_x), B, H, W, _stream()), "didfuse_stem_bwd")
         grads.append(d_x)
     return grads[0], grads[1]
+
+
+# ---------------------------------------------------------------------------------------------
+# BFFusion baseline (csrc/bffusion.hip, csrc/conv_slab.h; fusion_model/bffusion.py is the module)
+# ---------------------------------------------------------------------------------------------
+BFF_NB = (16, 32, 64, 96)        # channels of a level's encoder output, attention and fused map
+BFF_CIN = (16, 16, 32, 64)       # channels a level's DenseBlock starts from: its slab holds x | conv1 | conv2 = 3 cin
+BFF_HEADS = (4, 8, 8, 16)
+BFF_DCH = (96, 160, 224, 96)     # decoder slabs: up | f1 | x1_1 | x1_2 | x1_3;  up | f2 | x2_1 | x2_2;  up | f3 | x3_1;  f4
+BFF_FOFF = (32, 64, 96, 0)       # where the fused map sits in its level's slab
+# The six decoder convs in forward order (DB1_1, DB2_1, DB1_2, DB3_1, DB2_2, DB1_3): (level, level and offset of the map that is upsampled,
+# its channels, channels the conv reads = slab[0:K), offset of its output, output channels).  The upsampled map always lands in slab[0:C):
+# a conv's input is never needed again (only outputs are taped), so the three convs of level 1 share that slot one after the other.
+BFF_DEC = ((0, 1, 64, 32, 48, 48, 16), (1, 2, 96, 64, 96, 96, 32), (0, 1, 96, 32, 64, 64, 16),
+           (2, 3, 0, 96, 160, 160, 64), (1, 2, 160, 64, 128, 128, 32), (0, 1, 128, 32, 80, 80, 16))
+BFF_DEC_STORE = (32, 64, 32, 160, 128, 80)   # reverse: channels the fold WRITES (the rest it adds to); the first reverse consumer writes all
+BFF_DEC_UPADD = (1, 1, 1, 0, 0, 0)           # reverse: the upsample's transpose adds to (1) or writes (0) the source's gradient
+_EPI_ACT, _EPI_STORE, _EPI_ADD = 0, 1, 2
+
+
+def _po(t, off=0):
+    """Device pointer of channel `off` of a dense fp32 NHWC map."""
+    assert t.is_cuda and t.dtype == torch.float32 and t.is_contiguous() and 0 <= off < t.shape[-1]
+    return ctypes.c_void_p(t.data_ptr() + 4 * off)
+
+
+class _BffConv:
+    """One conv's operand packs (forward and transposed), bias, shape and form."""
+
+    __slots__ = ("fwd", "tr", "bias", "M", "K", "taps", "slope", "refl")
+
+    def __init__(self, parts, co, K, taps, bias, slope, refl):
+        L = lib()
+        dev = parts[0][0].device
+        self.M, self.K, self.taps, self.slope, self.refl = co, K, taps, float(slope), refl
+        self.fwd = torch.zeros(L.paif_bffusion_ops_floats(co, K, taps), device=dev, dtype=torch.float32)
+        self.tr = torch.zeros(L.paif_bffusion_ops_floats(K, co, taps), device=dev, dtype=torch.float32)
+        for w, off in parts:
+            w = w.detach().to(torch.float32).contiguous()
+            assert w.shape[0] == co and w[0, 0].numel() == taps
+            _lib.check(L.paif_bffusion_pack_ops(_p(w), co, w.shape[1], off, co, K, taps, 0, _p(self.fwd), _stream()), "bffusion_pack_ops")
+            _lib.check(L.paif_bffusion_pack_ops(_p(w), co, w.shape[1], off, K, co, taps, 1, _p(self.tr), _stream()), "bffusion_pack_ops")
+        self.bias = None if bias is None else bias.detach().to(torch.float32).contiguous().clone()
+
+
+class BffusionPack:
+    """The packed weights of BFFR: stems and head as they are, every other conv as a _BffConv (BatchNorm folded in), LayerNorm affine."""
+
+    __slots__ = ("stem", "dense", "attn", "dec", "head")
+
+
+def _bff_fold(w, b, g, be, mu, var, eps):
+    """Eval-mode BatchNorm into weight and bias, fp32 on the device."""
+    scale = g.detach() * torch.rsqrt(var.detach() + eps)
+    return w.detach() * scale[:, None, None, None], be.detach() + (b.detach() - mu.detach()) * scale
+
+
+def bffusion_pack(spec):
+    """spec (BFFR._pack_spec): stem [2][(w, b)], dense [2][4][(w1, b1, w2, b2, wd, bd)], attn [4][2] dicts (convs: four (w, b, gamma, beta,
+    mean, var, eps) = conv_pre then ffn; wq, wk, wv, wp, bp, ln_w, ln_b, ln_eps), dec [6][(w, b)] in BFF_DEC order, head (w, b); stream 0
+    is the `_vi` modules with attn2, stream 1 the `_ir` modules with attn1 -> BffusionPack."""
+    pk = BffusionPack()
+    c = lambda t: t.detach().to(torch.float32).contiguous().clone()
+    pk.stem = [(c(w).reshape(16), c(b)) for w, b in spec["stem"]]
+    pk.head = (c(spec["head"][0]).reshape(16), c(spec["head"][1]))
+    pk.dense = []
+    for s in range(2):
+        row = []
+        for l in range(4):
+            cin, w1, b1, w2, b2, wd, bd = (BFF_CIN[l],) + tuple(spec["dense"][s][l])
+            row.append((_BffConv([(w1, 0)], cin, cin, 9, b1, 0.2, 0), _BffConv([(w2, 0)], cin, 2 * cin, 9, b2, 0.2, 0),
+                        _BffConv([(wd, 0)], BFF_NB[l], 3 * cin, 1, bd, 0.1, 0)))
+        pk.dense.append(row)
+    pk.attn = []
+    for l in range(4):
+        dim, row = BFF_NB[l], []
+        for s in range(2):
+            a = spec["attn"][l][s]
+            convs = []
+            for w, b, g, be, mu, var, eps in a["convs"]:
+                wf, bf = _bff_fold(w, b, g, be, mu, var, float(eps))
+                convs.append(_BffConv([(wf, 0)], dim, dim, 9, bf, 0.0, 1))
+            qkv = torch.cat([a["wq"].detach(), a["wk"].detach(), a["wv"].detach()], 0).reshape(3 * dim, dim, 1, 1)
+            row.append(dict(convs=convs, qkv=_BffConv([(qkv, 0)], 3 * dim, dim, 1, None, 1.0, 0),
+                            proj=_BffConv([(a["wp"].detach().reshape(dim, dim, 1, 1), 0)], dim, dim, 1, a["bp"], 1.0, 0),
+                            ln_w=c(a["ln_w"]), ln_b=c(a["ln_b"]), ln_eps=float(a["ln_eps"]), d=dim // BFF_HEADS[l]))
+        pk.attn.append(row)
+    pk.dec = []
+    for (lvl, _, _, cup, K, _, M), (w, b) in zip(BFF_DEC, spec["dec"]):
+        # the reference's concat is (fused, earlier outputs ..., upsampled); the slab holds the upsampled map first
+        rest = K - cup
+        pk.dec.append(_BffConv([(w.detach()[:, :rest], cup), (w.detach()[:, rest:], 0)], M, K, 9, b, 0.01, 1))
+    return pk
+
+
+def _bff_conv(cv, src, src_off, dst, dst_off, B, H, W):
+    """Forward launch of a _BffConv: channels [src_off, + K) of src -> [dst_off, + M) of dst."""
+    epi = _EPI_STORE if cv.bias is None else _EPI_ACT
+    assert src_off + cv.K <= src.shape[-1] and dst_off + cv.M <= dst.shape[-1] and src.shape[:3] == dst.shape[:3] == (B, H, W)
+    _lib.check(lib().paif_bffusion_conv(_p(cv.fwd), _p(cv.bias), cv.slope, epi, cv.taps, cv.refl, _po(src, src_off), None, src.shape[-1], cv.K,
+                                        _po(dst, dst_off), dst.shape[-1], cv.M, B, H, W, _stream()), "bffusion_conv")
+
+
+def _bff_conv_t(cv, taped, d_out, out_off, d_in, in_off, ring, add, n_store, B, H, W):
+    """Transposed launch: the cotangent d_out[out_off, + M), masked by the taped output (null: no activation), -> d_in[in_off, + K).
+    A reflected conv goes through the ring map and the fold (n_store channels written, the rest added to); a zero-pad one writes or adds."""
+    L = lib()
+    assert out_off + cv.M <= d_out.shape[-1] and in_off + cv.K <= d_in.shape[-1] and d_out.shape[:3] == d_in.shape[:3] == (B, H, W)
+    mask = None if taped is None else _po(taped, out_off)
+    assert taped is None or taped.shape == d_out.shape
+    if cv.refl:
+        assert ring.numel() >= B * (H + 2) * (W + 2) * cv.K
+        _lib.check(L.paif_bffusion_conv(_p(cv.tr), None, cv.slope, _EPI_STORE, 9, 2, _po(d_out, out_off), mask, d_out.shape[-1], cv.M, _p(ring), cv.K,
+                                        cv.K, B, H, W, _stream()), "bffusion_conv")
+        _lib.check(L.paif_bffusion_fold(_p(ring), cv.K, n_store, _po(d_in, in_off), d_in.shape[-1], B, H, W, _stream()), "bffusion_fold")
+    else:
+        _lib.check(L.paif_bffusion_conv(_p(cv.tr), None, cv.slope, _EPI_ADD if add else _EPI_STORE, cv.taps, 0, _po(d_out, out_off), mask,
+                                        d_out.shape[-1], cv.M, _po(d_in, in_off), d_in.shape[-1], cv.K, B, H, W, _stream()), "bffusion_conv")
+
+
+def bffusion_forward(x0, x1, pack):
+    """Two [B,1,H,W] planes (x0 -> the `_vi` modules, x1 -> the `_ir` modules; H, W >= 16) -> (maps, fused [B,1,H,W]).  maps (fp32 NHWC):
+    E[s][l] the DenseBlock slabs x | conv1 | conv2; EN[s][l] the encoder outputs; A[l][s] per attention block p1, p2 (conv_pre), qkv, ctx
+    [B,dim,d], y (end_proj1), z (LayerNorm), f1, f2 (ffn); D[l] the decoder slabs (BFF_DCH; slot [0:C) holds the LAST upsampled map)."""
+    B, _, H, W = x0.shape
+    L, dev = lib(), x0.device
+    st = _stream
+    sizes = [(H >> l, W >> l) for l in range(4)]
+
+    def new(l, c, dtype=torch.float32):
+        return torch.empty((B, sizes[l][0], sizes[l][1], c), device=dev, dtype=dtype)
+
+    E = [[new(l, 3 * BFF_CIN[l]) for l in range(4)] for _ in range(2)]
+    EN = [[new(l, BFF_NB[l]) for l in range(4)] for _ in range(2)]
+    D = [new(l, BFF_DCH[l]) for l in range(4)]
+    for s, x in enumerate((x0, x1)):
+        keep, p, sb = _plane(x)
+        w, b = pack.stem[s]
+        _lib.check(L.paif_bffusion_stem_fwd(p, sb, _p(w), _p(b), _p(E[s][0]), 48, B, H, W, st()), "bffusion_stem_fwd")
+        for l in range(4):
+            h, wd = sizes[l]
+            cin, (c1, c2, cd) = BFF_CIN[l], pack.dense[s][l]
+            _bff_conv(c1, E[s][l], 0, E[s][l], cin, B, h, wd)
+            _bff_conv(c2, E[s][l], 0, E[s][l], 2 * cin, B, h, wd)
+            _bff_conv(cd, E[s][l], 0, EN[s][l], 0, B, h, wd)
+            if l < 3:
+                _lib.check(L.paif_bffusion_pool_fwd(_p(EN[s][l]), BFF_NB[l], BFF_NB[l], _p(E[s][l + 1]), 3 * BFF_CIN[l + 1], B, h, wd, st()),
+                           "bffusion_pool_fwd")
+    A = []
+    for l in range(4):
+        h, wd = sizes[l]
+        dim, row = BFF_NB[l], []
+        chunks = L.paif_bffusion_ctx_chunks(h, wd)
+        for s in range(2):
+            a = pack.attn[l][s]
+            d = a["d"]
+            m = dict(p1=new(l, dim), p2=new(l, dim), qkv=new(l, 3 * dim), y=new(l, dim), z=new(l, dim), f1=new(l, dim), f2=new(l, dim),
+                     ctx=torch.empty((B, dim, d), device=dev, dtype=torch.float32))
+            xa = new(l, dim)
+            partial = torch.empty((B, chunks, dim * d), device=dev, dtype=torch.float64)
+            _bff_conv(a["convs"][0], EN[s][l], 0, m["p1"], 0, B, h, wd)
+            _bff_conv(a["convs"][1], m["p1"], 0, m["p2"], 0, B, h, wd)
+            _bff_conv(a["qkv"], m["p2"], 0, m["qkv"], 0, B, h, wd)
+            _lib.check(L.paif_bffusion_ctx_partial(_po(m["qkv"], 0), 3 * dim, _po(m["qkv"], dim), 3 * dim, dim, d, _pd(partial), B, h, wd, st()),
+                       "bffusion_ctx_partial")
+            _lib.check(L.paif_bffusion_ctx_softmax(_pd(partial), dim, d, float(d) ** -0.5, _p(m["ctx"]), B, h, wd, st()), "bffusion_ctx_softmax")
+            _lib.check(L.paif_bffusion_attn_apply_fwd(_p(m["qkv"]), _p(m["ctx"]), dim, d, _p(xa), B, h, wd, st()), "bffusion_attn_apply_fwd")
+            _bff_conv(a["proj"], xa, 0, m["y"], 0, B, h, wd)
+            _lib.check(L.paif_bffusion_ln_fwd(_p(m["y"]), _p(a["ln_w"]), _p(a["ln_b"]), a["ln_eps"], dim, _p(m["z"]), B, h, wd, st()), "bffusion_ln_fwd")
+            _bff_conv(a["convs"][2], m["z"], 0, m["f1"], 0, B, h, wd)
+            _bff_conv(a["convs"][3], m["f1"], 0, m["f2"], 0, B, h, wd)
+            row.append(m)
+        # FusionBlock_res: (attn1(en_ir) + attn2(en_vi)) / 2 -- stream 1 is the `_ir` stream
+        _lib.check(L.paif_bffusion_gate_fwd(_p(EN[1][l]), dim, _p(row[1]["f2"]), _p(EN[0][l]), dim, _p(row[0]["f2"]), dim, _po(D[l], BFF_FOFF[l]),
+                                            BFF_DCH[l], B, h, wd, st()), "bffusion_gate_fwd")
+        A.append(row)
+    for cv, (lvl, sl, soff, cup, K, ooff, M) in zip(pack.dec, BFF_DEC):
+        h, wd = sizes[lvl]
+        assert sizes[sl] == (h // 2, wd // 2)
+        _lib.check(L.paif_bffusion_up_fwd(_po(D[sl], soff), BFF_DCH[sl], cup, _p(D[lvl]), BFF_DCH[lvl], B, h, wd, st()), "bffusion_up_fwd")
+        _bff_conv(cv, D[lvl], 0, D[lvl], ooff, B, h, wd)
+    fused = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    _lib.check(L.paif_bffusion_head_fwd(_p(pack.head[0]), _p(pack.head[1]), _po(D[0], 80), 96, _p(fused), B, H, W, st()), "bffusion_head_fwd")
+    return dict(E=E, EN=EN, A=A, D=D), fused
+
+
+def _pd(t):
+    """Device pointer of a dense float64 CUDA tensor (the context reduction's partial sums)."""
+    if not t.is_cuda or t.dtype != torch.float64 or not t.is_contiguous():
+        raise RuntimeError("expected a dense float64 CUDA tensor")
+    return ctypes.c_void_p(t.data_ptr())
+
+
+def bffusion_backward(maps, fused, d_fused, pack):
+    """Reverse of bffusion_forward (input gradients) from the taped maps and fused plane -> (d_x0, d_x1) [B,1,H,W].  Nothing is recomputed
+    but the LayerNorm statistics; no memset."""
+    B, _, H, W = fused.shape
+    L, dev = lib(), fused.device
+    st = _stream
+    d_fused = d_fused.contiguous()
+    E, EN, A, D = maps["E"], maps["EN"], maps["A"], maps["D"]
+    sizes = [(H >> l, W >> l) for l in range(4)]
+    # the ring map of the largest reflected transpose
+    ring_n = max([B * (sizes[l][0] + 2) * (sizes[l][1] + 2) * K for (l, _, _, _, K, _, _) in BFF_DEC] +
+                 [B * (sizes[l][0] + 2) * (sizes[l][1] + 2) * BFF_NB[l] for l in range(4)])
+    ring = torch.empty(ring_n, device=dev, dtype=torch.float32)
+    dD = [torch.empty_like(t) for t in D]
+    _lib.check(L.paif_bffusion_head_bwd(_p(pack.head[0]), _p(fused), _p(d_fused), _po(dD[0], 80), 96, B, H, W, st()), "bffusion_head_bwd")
+    for k in range(5, -1, -1):
+        lvl, sl, soff, cup, K, ooff, M = BFF_DEC[k]
+        h, wd = sizes[lvl]
+        _bff_conv_t(pack.dec[k], D[lvl], dD[lvl], ooff, dD[lvl], 0, ring, False, BFF_DEC_STORE[k], B, h, wd)
+        _lib.check(L.paif_bffusion_up_bwd(_p(dD[lvl]), BFF_DCH[lvl], cup, _po(dD[sl], soff), BFF_DCH[sl], BFF_DEC_UPADD[k], B, h, wd, st()),
+                   "bffusion_up_bwd")
+    grads = []
+    for s in range(2):
+        dE = [torch.empty_like(t) for t in E[s]]
+        for l in range(3, -1, -1):
+            h, wd = sizes[l]
+            dim, cin, a, m = BFF_NB[l], BFF_CIN[l], pack.attn[l][s], A[l][s]
+            d = a["d"]
+            dEN = torch.empty_like(EN[s][l])
+            da, db, dqkv = torch.empty_like(dEN), torch.empty_like(dEN), torch.empty_like(m["qkv"])
+            dS = torch.empty_like(m["ctx"])
+            partial = torch.empty((B, L.paif_bffusion_ctx_chunks(h, wd), dim * d), device=dev, dtype=torch.float64)
+            # the gate and the mean: d_f2 -> da, d_skip -> dEN (written)
+            _lib.check(L.paif_bffusion_gate_bwd(_po(dD[l], BFF_FOFF[l]), BFF_DCH[l], _p(EN[s][l]), dim, _p(m["f2"]), dim, _p(da), _p(dEN), B, h, wd,
+                                                st()), "bffusion_gate_bwd")
+            _bff_conv_t(a["convs"][3], m["f2"], da, 0, db, 0, ring, False, dim, B, h, wd)      # -> d_f1
+            _bff_conv_t(a["convs"][2], m["f1"], db, 0, da, 0, ring, False, dim, B, h, wd)      # -> d_z
+            _lib.check(L.paif_bffusion_ln_bwd(_p(m["y"]), _p(a["ln_w"]), a["ln_eps"], dim, _p(da), _p(db), B, h, wd, st()), "bffusion_ln_bwd")
+            _bff_conv_t(a["proj"], None, db, 0, da, 0, ring, False, dim, B, h, wd)             # d_y -> d_x (the attention's output)
+            _lib.check(L.paif_bffusion_ctx_partial(_po(m["qkv"], 2 * dim), 3 * dim, _p(da), dim, dim, d, _pd(partial), B, h, wd, st()),
+                       "bffusion_ctx_partial")
+            _lib.check(L.paif_bffusion_ctx_softmax_bwd(_pd(partial), dim, d, float(d) ** -0.5, _p(m["ctx"]), _p(dS), B, h, wd, st()),
+                       "bffusion_ctx_softmax_bwd")
+            _lib.check(L.paif_bffusion_attn_apply_bwd(_p(m["qkv"]), _p(da), _p(m["ctx"]), _p(dS), dim, d, _p(dqkv), B, h, wd, st()),
+                       "bffusion_attn_apply_bwd")
+            _bff_conv_t(a["qkv"], None, dqkv, 0, db, 0, ring, False, dim, B, h, wd)            # -> d_p2
+            _bff_conv_t(a["convs"][1], m["p2"], db, 0, da, 0, ring, False, dim, B, h, wd)      # -> d_p1
+            _bff_conv_t(a["convs"][0], m["p1"], da, 0, dEN, 0, ring, False, 0, B, h, wd)       # adds to d_skip
+            if l < 3:
+                _lib.check(L.paif_bffusion_pool_bwd(_p(EN[s][l]), dim, dim, _p(dE[l + 1]), 3 * BFF_CIN[l + 1], _p(dEN), dim, B, h, wd, st()),
+                           "bffusion_pool_bwd")
+            c1, c2, cd = pack.dense[s][l]
+            _bff_conv_t(cd, EN[s][l], dEN, 0, dE[l], 0, ring, False, 0, B, h, wd)              # writes all 3 cin
+            _bff_conv_t(c2, E[s][l], dE[l], 2 * cin, dE[l], 0, ring, True, 0, B, h, wd)
+            _bff_conv_t(c1, E[s][l], dE[l], cin, dE[l], 0, ring, True, 0, B, h, wd)
+        d_x = torch.empty_like(fused)
+        _lib.check(L.paif_bffusion_stem_bwd(_p(pack.stem[s][0]), _p(dE[0]), 48, _p(d_x), B, H, W, st()), "bffusion_stem_bwd")
+        grads.append(d_x)
+    return grads[0], grads[1]

@@ -230,6 +230,71 @@ def didfuse_state_dict(scales, shift):
     return sd
 
 
+# The BFFusion baseline (reference fusion_model/BFFusion.py, class BFFR).  BFFUSION_LAYERS: its 97 convs and linears in state_dict order,
+# as (state_dict prefix of `.weight`, weight shape, has a bias, kind, BatchNorm prefix or None).  kind: "stem" (1 x 1, no activation),
+# "dense" (LeakyReLU 0.2 / 0.1), "fconv" (BatchNorm + ReLU: the 32 BatchNorms that ARE applied), "q", "k", "v", "proj" (the attention's
+# linears), "dec" (LeakyReLU 0.01; its `bn` is a member the reference never applies), "head" (tanh / 2 + 0.5).
+BFFUSION_NB, BFFUSION_CIN, BFFUSION_HEADS = (16, 32, 64, 96), (16, 16, 32, 64), (4, 8, 8, 16)
+
+
+def _bffusion_layers():
+    out = []
+    for tag in ("vi", "ir"):
+        out.append(("conv1_%s.conv2d" % tag, (16, 1, 1, 1), True, "stem", "conv1_%s.bn" % tag))
+        for l, (c, nb) in enumerate(zip(BFFUSION_CIN, BFFUSION_NB)):
+            db = "DB%d_%s" % (l + 1, tag)
+            out += [(db + ".conv1.conv", (c, c, 3, 3), True, "dense", None), (db + ".conv2.conv", (c, 2 * c, 3, 3), True, "dense", None),
+                    (db + ".conv_down", (nb, 3 * c, 1, 1), True, "dense", None)]
+    for l, dim in enumerate(BFFUSION_NB):
+        for at in ("attn1", "attn2"):
+            p = "fusion_block%d.%s" % (l + 1, at)
+            for seq in ("conv_pre", "ffn"):
+                for k in range(2):
+                    f = "%s.%s.%d" % (p, seq, k)
+                    out.append((f + ".conv2d", (dim, dim, 3, 3), True, "fconv", f + ".batch_norm"))
+            out += [(p + ".wq1", (dim, dim), False, "q", None), (p + ".wk1", (dim, dim), False, "k", None),
+                    (p + ".wv1", (dim, dim), False, "v", None), (p + ".end_proj1", (dim, dim), True, "proj", None)]
+    nb = BFFUSION_NB
+    for name, cin, cout in (("DB1_1", nb[0] + nb[1], nb[0]), ("DB2_1", nb[1] + nb[2], nb[1]), ("DB3_1", nb[2] + nb[3], nb[2]),
+                            ("DB1_2", 2 * nb[0] + nb[1], nb[0]), ("DB2_2", 2 * nb[1] + nb[2], nb[1]), ("DB1_3", 3 * nb[0] + nb[1], nb[0])):
+        out.append((name + ".conv2d", (cout, cin, 3, 3), True, "dec", name + ".bn"))
+    out.append(("conv_out.conv2d", (1, nb[0], 1, 1), True, "head", None))
+    return tuple(out)
+
+
+BFFUSION_LAYERS = _bffusion_layers()
+
+
+def bffusion_state_dict(scales, shifts=0.0):
+    """key -> numpy array (386 entries, the reference's state_dict order): formula_tensor("bff/" + key) times the layer's scale (weight
+    and bias alike), the layer's shift (one per layer, or one scalar for all) added to every element of its bias, and formula values -- not the identity -- for every BatchNorm (the 32 applied
+    ones and the 8 `ConvLayer.bn` that are never applied) and LayerNorm entry.  tools/make_golden_bffusion.py and the tests rebuild the
+    fixture weights with this one expression."""
+    scales = np.asarray(scales, dtype=np.float32)
+    shifts = np.broadcast_to(np.asarray(shifts, dtype=np.float32), scales.shape)
+    assert scales.shape == (len(BFFUSION_LAYERS),)
+    sd = {}
+
+    def norm(prefix, c, batch):
+        leaves = ("weight", "bias", "running_mean", "running_var") if batch else ("weight", "bias")
+        for leaf in leaves:
+            sd["%s.%s" % (prefix, leaf)] = formula_tensor("bff/%s.%s" % (prefix, leaf), (c,))
+        if c == 1:      # a one-element `weight` is a norm gain here, not a slope
+            sd[prefix + ".weight"] = (0.8 + 0.4 * hash_uniform(key_seed("bff/" + prefix + ".weight"), 1)).astype(np.float32)
+        if batch:
+            sd[prefix + ".num_batches_tracked"] = formula_tensor("bff/" + prefix + ".num_batches_tracked", ())
+
+    for (name, shape, bias, kind, bn), s, sh in zip(BFFUSION_LAYERS, scales, shifts):
+        if kind == "q":     # LayerNorm sits before the three linears in the state_dict
+            norm(name[:-len("wq1")] + "norm1", shape[0], False)
+        sd[name + ".weight"] = formula_tensor("bff/" + name + ".weight", shape) * s
+        if bias:
+            sd[name + ".bias"] = formula_tensor("bff/" + name + ".bias", (shape[0],)) * s + sh
+        if bn is not None:
+            norm(bn, shape[0], True)
+    return sd
+
+
 # --------------------------------------------------------------------------------------
 # inputs
 # --------------------------------------------------------------------------------------
