@@ -1033,6 +1033,48 @@ int paif_bffusion_attn_apply_fwd(const float* qkv, const float* ctx, int dim, in
 int paif_bffusion_attn_apply_bwd(const float* qkv, const float* d_x, const float* ctx, const float* d_s, int dim, int d, float* d_qkv, int B,
                                  int H, int W, paif_stream_t stream);
 
+/* The hand-designed fusion network (core/model_fusion_auto.py:118-188 of the reference: DRDB :118-158, Fusion_Network :159-188;
+ * csrc/drdb.hip, csrc/conv_slab.h).  fp32 throughout, NHWC maps.  One slab [B,H,W,224] per DRDB: x in [0, 64), x_k = ReLU(Dcov_k) in
+ * [64 + 32 (k - 1), 64 + 32 k); r6 [B,H,W,64] tapes ReLU(conv 1x1) of a block; c2 [B,H,W,32] is conv2's map, f [B,H,W] conv21's, BEFORE
+ * the clamp.  The clamp and the batch min / max normalisation of f are paif_plane_clamp_minmax_fwd / _bwd_input.  block: 0 DRDB1, 1 DRDB2.
+ * The one PReLU slope is an argument (>= 0: the reverse pass reads the branch off the taped output).  Gradient buffers use the layouts of
+ * their maps.  pack: paif_drdb_pack_floats() floats, ZEROED, then written by fifteen paif_drdb_pack_conv calls.  No host synchronisation,
+ * no allocation: capturable.  Bit-reproducible (no atomics). */
+size_t paif_drdb_pack_floats(void);
+/* One Conv2d into the kernels' layout.  conv = 0 conv1 (:162); 1 + 6 block + {0..4 Dcov1..Dcov5 (:122-130), 5 conv (:133)}; 13 conv2
+ * (:167); 14 conv21 (:168). */
+int paif_drdb_pack_conv(const float* w, const float* b, int conv, float* pack, paif_stream_t stream);
+/* :173-174: channels [0, 64) of DRDB1's slab = PReLU(conv 3x3, pad 1, 2 -> 64 of cat(ir, vis)); plane b of ir at ir + b * sb_ir, of vis
+ * at vis + b * sb_vis: no cat is materialised. */
+int paif_drdb_stem_fwd(const float* ir, size_t sb_ir, const float* vis, size_t sb_vis, const float* pack, float slope, float* slab, int B, int H,
+                       int W, paif_stream_t stream);
+/* :136-154: Dcov_k, k = 1..5: ReLU(conv 3x3, dilation 2, pad 2), an implicit GEMM on v_mfma_f32_16x16x4_f32 inside the block's slab:
+ * reads [0, 64 + 32 (k - 1)), writes the 32 channels behind them. */
+int paif_drdb_dcov_fwd(const float* pack, int block, int k, float* slab, int B, int H, int W, paif_stream_t stream);
+/* :156-157: out[0:64) = x + r, r = ReLU(conv 1x1 224 -> 64 of the slab), x = slab[0:64); out has out_cs = 224 (the next block's slab) or
+ * 64 channels per pixel; WRITES r to r6. */
+int paif_drdb_tail_fwd(const float* pack, int block, const float* slab, float* out, int out_cs, float* r6, int B, int H, int W,
+                       paif_stream_t stream);
+/* :178: c2 = PReLU(conv 3x3, pad 1, 64 -> 32 of the dense 64-channel map `in`). */
+int paif_drdb_conv2_fwd(const float* pack, float slope, const float* in, float* c2, int B, int H, int W, paif_stream_t stream);
+/* :179: f = PReLU(conv 3x3, pad 1, 32 -> 1 of c2), before the clamp of :180-183. */
+int paif_drdb_head_fwd(const float* pack, float slope, const float* c2, float* f, int B, int H, int W, paif_stream_t stream);
+/* Reverse of :179: d_f through the PReLU (branch from the taped f) and the transposed conv; WRITES d_c2. */
+int paif_drdb_head_bwd(const float* pack, float slope, const float* f, const float* d_f, float* d_c2, int B, int H, int W, paif_stream_t stream);
+/* Reverse of :178: d_c2 through the PReLU (branch from the taped c2) and the transposed conv; WRITES the dense 64-channel d_in. */
+int paif_drdb_conv2_bwd(const float* pack, float slope, const float* c2, const float* d_c2, float* d_in, int B, int H, int W,
+                        paif_stream_t stream);
+/* Reverse of :156-157, first of a block's six: d_out (its first 64 channels, pixel stride d_out_cs = 224 or 64) through the ReLU (branch
+ * from the taped r6) and the transposed 1x1 WRITES all 224 channels of d_slab; the residual then ADDS d_out onto [0, 64).  Two launches. */
+int paif_drdb_tail_bwd(const float* pack, int block, const float* r6, const float* d_out, int d_out_cs, float* d_slab, int B, int H, int W,
+                       paif_stream_t stream);
+/* Reverse of Dcov_k (k = 5 first): its 32 channels of d_slab through the ReLU (branch from the taped slab) and the transposed dilated
+ * conv, ADDED into the channels below them. */
+int paif_drdb_dcov_bwd(const float* pack, int block, int k, const float* slab, float* d_slab, int B, int H, int W, paif_stream_t stream);
+/* Reverse of :173-174: channels [0, 64) of DRDB1's d_slab through the PReLU and the transposed conv -> d_ir, d_vis [B,H,W] (written). */
+int paif_drdb_stem_bwd(const float* pack, float slope, const float* slab, const float* d_slab, float* d_ir, float* d_vis, int B, int H, int W,
+                       paif_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,7 +3,9 @@ MI355X-native counterparts of the reference's core/model_fusion_auto.py classes 
 path (SURVEY.md 8(a): F1-F8, G1, S1).  Same names, constructor signatures and state_dict keys;
 forward() bodies launch the hand-written gfx950 kernels of libpaif_hip.so.
 
-Not reproduced (out of scope, never constructed by either entry script): DRDB, Fusion_Network*,
+DRDB and Fusion_Network (:118-188, the hand-designed network) live in fusion_model/drdb.py and are exported from here.
+
+Not reproduced (out of scope, never constructed by either entry script): Fusion_Network2 / _auto / _Add / ...,
 SKFF, the GAN pieces, Network_MM_TARDAL/UMF/Base/Auto, the *_showfeatures variants.
 """
 import torch
@@ -917,3 +919,7 @@ class Network_MM_SearchedFusion(nn.Module):
 
     def enhance_net_parameters(self):
         return self.enhance_net.parameters()
+
+
+# the hand-designed fusion network of :118-188 (imported last: fusion_model/drdb.py needs nothing of this module)
+from ..fusion_model.drdb import DRDB, Fusion_Network  # noqa: E402,F401

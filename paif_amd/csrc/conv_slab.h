@@ -10,8 +10,12 @@
 //   * REFL: REFL_STAGE stages the halo by REFLECTION (row -1 takes row 1, row H takes row H - 2: ReflectionPad2d(1) in front of the conv);
 //     REFL_RING is the transpose's half of that: the zero-pad conv evaluated on the (H + 2) x (W + 2) grid, the input read one pixel up
 //     and left, the output a ring map [B][H + 2][W + 2][out_cs] that a fold pass adds back onto the plane (bffusion.hip: fold_k).
+//   * DIL: the dilation of the 3 x 3 taps, 1 or 2 (zero pad DIL): the staged tile has a halo of DIL (20 x 20 pixels at 2; with MB = 4
+//     the static LDS is 4 * 400 + 9 * 4 * 64 float4 = 62464 B of the 64 KB), tap t reads at + DIL (t / 3) rows and + DIL (t % 3) columns;
+//   * EPI_RES (1 x 1 only): the residual AFTER the activation, out = x + act(v + b) with x the first channels of the INPUT map at the same
+//     pixel; act(v + b) itself goes to `avg` (the tape of the branch: x + r can equal x in fp32 for a small positive r).
 //   ReLU is LeakyReLU at slope 0, epilogue and mask alike (a negative input stores -0, which every consumer treats as 0).
-// The last four default to what the header did before them: an instantiation that does not name them compiles to the same code.
+// The last five default to what the header did before them: an instantiation that does not name them compiles to the same code.
 // Everything else is conv_k's.  Output CHANNELS on M, 16 PIXELS of one image row on N; the D operand of lane l is channels
 // 4 (l >> 4) .. + 3 of pixel l & 15, one float4 of the NHWC map, and the B operand of four consecutive instructions is one float4 of the
 // input map.  A workgroup of four waves owns a 16 x 16 pixel tile (four rows per wave) and MB blocks of 16 output channels (blockIdx.y
@@ -29,7 +33,7 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 
 constexpr int DT = 16;   // tile edge: 4 waves x 4 rows of 16 pixels
 
-enum { EPI_ACT = 0, EPI_STORE = 1, EPI_ADD = 2 };
+enum { EPI_ACT = 0, EPI_STORE = 1, EPI_ADD = 2, EPI_RES = 3 };
 enum { ACT_LEAKY = 0, ACT_TANH = 1 };
 enum { XIN_PLAIN = 0, XIN_SCALED = 1, XIN_SUM = 2 };
 enum { REFL_NONE = 0, REFL_STAGE = 1, REFL_RING = 2 };
@@ -93,11 +97,12 @@ struct ConvArgs {
   const float* mask;    // MASK: the taped map of the same slice (same stride)
   float* out;           // first channel of the output map; pixel stride out_cs; channels [out_off, out_off + out_n) are written
   const float* wpk;     // operand pack of this conv
-  const float* bias;    // EPI_ACT
+  const float* bias;    // EPI_ACT, EPI_RES
   const float* bias2;   // EPI_ACT: a second bias, or null
   float slope;          // LeakyReLU slope: of the stored map (EPI_ACT), of the taped map behind the input (MASK)
   int in_cs, nq, out_cs, out_off, out_n, chunks, H, W, tx, ty;
   // PAIR: `pair` is laid out as `out` (same stride and offset); 0.5 (own + pair) goes to channels [avg_off, avg_off + out_n) of `avg`
+  // EPI_RES: act(v + b) goes to channels [avg_off, avg_off + out_n) of `avg`; the residual is channels [0, out_n) of `in`
   const float* pair = nullptr;
   float* avg = nullptr;
   int avg_cs = 0, avg_off = 0;
@@ -107,13 +112,15 @@ struct ConvArgs {
   int mask_cs = 0;
 };
 
-template <int TAPS, int MB, bool MASK, int EPI, int ACT = ACT_LEAKY, bool PAIR = false, int XIN = XIN_PLAIN, int REFL = REFL_NONE>
+template <int TAPS, int MB, bool MASK, int EPI, int ACT = ACT_LEAKY, bool PAIR = false, int XIN = XIN_PLAIN, int REFL = REFL_NONE, int DIL = 1>
 __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
   static_assert(TAPS == 9 || TAPS == 1, "3 x 3 or 1 x 1");
   static_assert(!PAIR || EPI == EPI_ACT, "the pair store belongs to the activation epilogue");
   static_assert(XIN == XIN_PLAIN || MASK, "the extended staging is the masked one");
   static_assert(REFL == REFL_NONE || (TAPS == 9 && !PAIR && XIN == XIN_PLAIN), "reflection belongs to the plain 3 x 3 forms");
-  constexpr int HALO = TAPS == 9 ? 1 : 0, DP = DT + 2 * HALO;
+  static_assert(DIL == 1 || (DIL == 2 && TAPS == 9 && REFL == REFL_NONE), "dilation 2 belongs to the zero-padded 3 x 3 forms");
+  static_assert(EPI != EPI_RES || (TAPS == 1 && !MASK && !PAIR), "the residual epilogue belongs to the forward 1 x 1");
+  constexpr int HALO = TAPS == 9 ? DIL : 0, DP = DT + 2 * HALO;
   constexpr int QS = (DP * DP + 15) / 16 * 16;   // quad stride in float4, a multiple of 256 B: quad planes start at the same LDS bank
   __shared__ float4 s_x[4 * QS];
   __shared__ float4 s_w[TAPS * MB * 64];
@@ -165,7 +172,7 @@ __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
     for (int tap = 0; tap < TAPS; ++tap) {
       float4 xv[4];
 #pragma unroll
-      for (int r = 0; r < 4; ++r) xv[r] = s_x[q * QS + (r0 + r + (HALO ? tap / 3 : 0)) * DP + p + (HALO ? tap % 3 : 0)];
+      for (int r = 0; r < 4; ++r) xv[r] = s_x[q * QS + (r0 + r + (HALO ? DIL * (tap / 3) : 0)) * DP + p + (HALO ? DIL * (tap % 3) : 0)];
 #pragma unroll
       for (int mb = 0; mb < MB; ++mb) {
         const float4 wv = s_w[(tap * MB + mb) * 64 + lane];
@@ -188,7 +195,7 @@ __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
     const int co = 16 * ((int)blockIdx.y * MB + mb) + 4 * q;   // out_n is a multiple of 4: a quad is written whole or not at all
     if (co >= a.out_n) continue;
     float4 bs = make_float4(0.f, 0.f, 0.f, 0.f);
-    if constexpr (EPI == EPI_ACT) {
+    if constexpr (EPI == EPI_ACT || EPI == EPI_RES) {
       bs = *reinterpret_cast<const float4*>(a.bias + co);
       if (a.bias2) {
         const float4 b2 = *reinterpret_cast<const float4*>(a.bias2 + co);
@@ -211,6 +218,12 @@ __global__ __launch_bounds__(256, 2) void conv_k(const ConvArgs a) {
           *reinterpret_cast<float4*>(a.avg + px * a.avg_cs + a.avg_off + co) =
               make_float4(0.5f * (u.x + f.x), 0.5f * (u.y + f.y), 0.5f * (u.z + f.z), 0.5f * (u.w + f.w));
         }
+      } else if constexpr (EPI == EPI_RES) {   // the input map is not the output map: its quad is read, never written, by this launch
+        const float4 f = make_float4(act_of<ACT>(v[0] + bs.x, a.slope), act_of<ACT>(v[1] + bs.y, a.slope), act_of<ACT>(v[2] + bs.z, a.slope),
+                                     act_of<ACT>(v[3] + bs.w, a.slope));
+        const float4 u = *reinterpret_cast<const float4*>(a.in + px * a.in_cs + co);
+        *reinterpret_cast<float4*>(a.avg + px * a.avg_cs + a.avg_off + co) = f;
+        *o = make_float4(u.x + f.x, u.y + f.y, u.z + f.z, u.w + f.w);
       } else if constexpr (EPI == EPI_STORE) {
         *o = make_float4(v[0], v[1], v[2], v[3]);
       } else {

@@ -2832,3 +2832,116 @@ def bffusion_backward(maps, fused, d_fused, pack):
         _lib.check(L.paif_bffusion_stem_bwd(_p(pack.stem[s][0]), _p(dE[0]), 48, _p(d_x), B, H, W, st()), "bffusion_stem_bwd")
         grads.append(d_x)
     return grads[0], grads[1]
+
+
+# ---------------------------------------------------------------------------------------------
+# The hand-designed fusion network: Fusion_Network over two DRDB (csrc/drdb.hip, csrc/conv_slab.h; fusion_model/drdb.py is the module)
+# ---------------------------------------------------------------------------------------------
+class DrdbPack:
+    """The packed weights of Fusion_Network and its one PReLU slope as a Python float."""
+
+    __slots__ = ("weights", "slope")
+
+    def __init__(self, weights, slope):
+        self.weights, self.slope = weights, float(slope)
+
+
+def drdb_pack(convs, slope=0.0):
+    """convs: (weight, bias) per conv, by position in paif_amd.synthetic.DRDB_CONVS order (conv1, DRDB1.Dcov1..5, DRDB1.conv, DRDB2.*, conv2,
+    conv21); an entry may be None (a DRDB alone packs its own six at positions 1..6 and leaves the rest as zeros).  slope: the PReLU slope
+    (a one-element tensor or a float), read to the host HERE, once per pack -> DrdbPack.  A negative slope is refused: the reverse pass
+    reads the PReLU branch off the taped output."""
+    if len(convs) != 15:
+        raise ValueError("drdb_pack: fifteen convs are expected, got %d" % len(convs))
+    host = float(slope.detach().reshape(-1)[0]) if torch.is_tensor(slope) else float(slope)
+    if not host >= 0.0:
+        raise ValueError("Fusion_Network: the PReLU slope is %g; the reverse pass reads the branch off the taped output, which is right for "
+                         "slopes >= 0 only" % host)
+    dev = next(c for c in convs if c is not None)[0].device
+    pack = torch.zeros(lib().paif_drdb_pack_floats(), device=dev, dtype=torch.float32)
+    for conv, c in enumerate(convs):
+        if c is not None:
+            _lib.check(lib().paif_drdb_pack_conv(_p(c[0].detach().contiguous()), _p(c[1].detach().contiguous()), conv, _p(pack), _stream()),
+                       "drdb_pack_conv")
+    return DrdbPack(pack, host)
+
+
+def _drdb_block_fwd(wp, block, slab, out, r6, B, H, W):
+    L = lib()
+    for k in range(1, 6):
+        _lib.check(L.paif_drdb_dcov_fwd(wp, block, k, _p(slab), B, H, W, _stream()), "drdb_dcov_fwd")
+    _lib.check(L.paif_drdb_tail_fwd(wp, block, _p(slab), _p(out), out.shape[-1], _p(r6), B, H, W, _stream()), "drdb_tail_fwd")
+
+
+def _drdb_block_bwd(wp, block, slab, r6, d_out, d_slab, B, H, W):
+    """d_out: the first 64 channels of a dense [B,H,W,224 | 64] map; d_slab: written whole, [..., 0:64] ends as the gradient of x."""
+    L = lib()
+    _lib.check(L.paif_drdb_tail_bwd(wp, block, _p(r6), _p(d_out), d_out.shape[-1], _p(d_slab), B, H, W, _stream()), "drdb_tail_bwd")
+    for k in range(5, 0, -1):
+        _lib.check(L.paif_drdb_dcov_bwd(wp, block, k, _p(slab), _p(d_slab), B, H, W, _stream()), "drdb_dcov_bwd")
+
+
+def drdb_forward(ir, vis, pack):
+    """Two [B,1,H,W] planes (channel 0 of the reference's ir and vis) -> (maps, fused [B,1,H,W]).  maps: slab [B,H,W,224] and r6 [B,H,W,64]
+    per DRDB, f2 [B,H,W,64] (DRDB2's output), c2 [B,H,W,32], f [B,1,H,W] (conv21's PReLU output BEFORE the clamp), all fp32, and minmax:
+    the 2 floats (min, max of the clamped f over the whole batch).  17 launches."""
+    B, _, H, W = ir.shape
+    L = lib()
+    dev = ir.device
+    (_, p_ir, sb_ir), (_, p_vis, sb_vis) = keep = (_plane(ir), _plane(vis))
+
+    def new(c):
+        return torch.empty((B, H, W, c), device=dev, dtype=torch.float32)
+
+    wp, sl = _p(pack.weights), pack.slope
+    slab, r6, f2, c2 = [new(224), new(224)], [new(64), new(64)], new(64), new(32)
+    f = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    _lib.check(L.paif_drdb_stem_fwd(p_ir, sb_ir, p_vis, sb_vis, wp, sl, _p(slab[0]), B, H, W, _stream()), "drdb_stem_fwd")
+    _drdb_block_fwd(wp, 0, slab[0], slab[1], r6[0], B, H, W)
+    _drdb_block_fwd(wp, 1, slab[1], f2, r6[1], B, H, W)
+    _lib.check(L.paif_drdb_conv2_fwd(wp, sl, _p(f2), _p(c2), B, H, W, _stream()), "drdb_conv2_fwd")
+    _lib.check(L.paif_drdb_head_fwd(wp, sl, _p(c2), _p(f), B, H, W, _stream()), "drdb_head_fwd")
+    fused, mm = plane_clamp_minmax(f)
+    del keep
+    return dict(slab=slab, r6=r6, f2=f2, c2=c2, f=f, minmax=mm), fused
+
+
+def drdb_backward(maps, d_fused, pack):
+    """Reverse of drdb_forward (input gradients) from the taped maps -> (d_ir, d_vis) [B,1,H,W].  19 launches; nothing is recomputed and
+    nothing needs a memset.  The extremum terms of the normalisation follow torch (paif_plane_clamp_minmax_bwd_input): they reach an
+    extremal pixel only where the clamp passes."""
+    B, _, H, W = maps["f"].shape
+    L = lib()
+    wp, sl = _p(pack.weights), pack.slope
+    d_f = plane_clamp_minmax_bwd(d_fused, maps["f"], maps["minmax"])
+    d_c2, d_f2 = torch.empty_like(maps["c2"]), torch.empty_like(maps["f2"])
+    d_slab = [torch.empty_like(maps["slab"][0]), torch.empty_like(maps["slab"][1])]
+    _lib.check(L.paif_drdb_head_bwd(wp, sl, _p(maps["f"]), _p(d_f), _p(d_c2), B, H, W, _stream()), "drdb_head_bwd")
+    _lib.check(L.paif_drdb_conv2_bwd(wp, sl, _p(maps["c2"]), _p(d_c2), _p(d_f2), B, H, W, _stream()), "drdb_conv2_bwd")
+    _drdb_block_bwd(wp, 1, maps["slab"][1], maps["r6"][1], d_f2, d_slab[1], B, H, W)
+    _drdb_block_bwd(wp, 0, maps["slab"][0], maps["r6"][0], d_slab[1], d_slab[0], B, H, W)
+    d_ir, d_vis = torch.empty_like(maps["f"]), torch.empty_like(maps["f"])
+    _lib.check(L.paif_drdb_stem_bwd(wp, sl, _p(maps["slab"][0]), _p(d_slab[0]), _p(d_ir), _p(d_vis), B, H, W, _stream()), "drdb_stem_bwd")
+    return d_ir, d_vis
+
+
+def drdb_block_forward(x, pack):
+    """One DRDB alone: x [B,64,H,W] fp32 NCHW -> (maps, out [B,64,H,W]).  The block's weights sit at DRDB1's place in the pack.  maps: slab
+    [B,H,W,224] and r6 [B,H,W,64].  Six launches between two layout copies."""
+    B, C, H, W = x.shape
+    if C != 64:
+        raise ValueError("DRDB: a [B,64,H,W] map is expected (in_ch = 64, growth_rate = 32 is the built form), got %s" % (tuple(x.shape),))
+    slab = torch.empty((B, H, W, 224), device=x.device, dtype=torch.float32)
+    slab[..., 0:64].copy_(x.permute(0, 2, 3, 1))
+    out, r6 = (torch.empty((B, H, W, 64), device=x.device, dtype=torch.float32) for _ in range(2))
+    _drdb_block_fwd(_p(pack.weights), 0, slab, out, r6, B, H, W)
+    return dict(slab=slab, r6=r6), out.permute(0, 3, 1, 2).contiguous()
+
+
+def drdb_block_backward(maps, d_out, pack):
+    """Reverse of drdb_block_forward: d_out [B,64,H,W] -> d_x [B,64,H,W]."""
+    B, H, W, _ = maps["slab"].shape
+    g = d_out.permute(0, 2, 3, 1).contiguous()
+    d_slab = torch.empty_like(maps["slab"])
+    _drdb_block_bwd(_p(pack.weights), 0, maps["slab"], maps["r6"], g, d_slab, B, H, W)
+    return d_slab[..., 0:64].permute(0, 3, 1, 2).contiguous()

@@ -230,6 +230,35 @@ def didfuse_state_dict(scales, shift):
     return sd
 
 
+# The fifteen Conv2d of the hand-designed Fusion_Network (reference core/model_fusion_auto.py:159-188, its two DRDB :118-158) in
+# state_dict order, as (name, out channels, in channels, kernel size): the order of ops.drdb_pack.
+def _drdb_convs(prefix):
+    return tuple(("%s.Dcov%d" % (prefix, k), 32, 64 + 32 * (k - 1), 3) for k in range(1, 6)) + ((prefix + ".conv", 64, 224, 1),)
+
+
+DRDB_CONVS = (("conv1", 64, 2, 3),) + _drdb_convs("DRDB1") + _drdb_convs("DRDB2") + (("conv2", 32, 64, 3), ("conv21", 1, 32, 3))
+# Prefix of the formula keys.  The draw matters to the fixture tool: with most prefixes conv21's output is one-signed on the calibration planes
+# (negative share under 0.2 or over 0.8), which tools/make_golden_drdb.py refuses; "hand/" (the hand-designed network) calibrates.
+DRDB_PREFIX = "hand/"
+
+
+def drdb_state_dict(scales, shift=0.0, last_scale=1.0):
+    """key -> numpy array (31 entries, the reference's state_dict order): formula_tensor(DRDB_PREFIX + key) times the conv's scale (weight and
+    bias alike); conv21's weight and bias are further multiplied by `last_scale` and `shift` is then added to its bias; relu.weight (the
+    one PReLU slope) is the formula value, in [0.1, 0.3).  (shift, last_scale) = (0, 1) is weight set A of tools/make_golden_drdb.py (both
+    clamps active), (0.5, 0.1) is set B (no pixel clamped).  The tool and the tests rebuild the fixture weights with this one expression."""
+    scales = np.asarray(scales, dtype=np.float32)
+    assert scales.shape == (len(DRDB_CONVS),)
+    sd = {}
+    for (name, cout, cin, k), s in zip(DRDB_CONVS, scales):
+        sd[name + ".weight"] = formula_tensor(DRDB_PREFIX + name + ".weight", (cout, cin, k, k)) * s
+        sd[name + ".bias"] = formula_tensor(DRDB_PREFIX + name + ".bias", (cout,)) * s
+    sd["conv21.weight"] = sd["conv21.weight"] * np.float32(last_scale)
+    sd["conv21.bias"] = sd["conv21.bias"] * np.float32(last_scale) + np.float32(shift)
+    sd["relu.weight"] = formula_tensor(DRDB_PREFIX + "relu.weight", (1,))
+    return sd
+
+
 # The BFFusion baseline (reference fusion_model/BFFusion.py, class BFFR).  BFFUSION_LAYERS: its 97 convs and linears in state_dict order,
 # as (state_dict prefix of `.weight`, weight shape, has a bias, kind, BatchNorm prefix or None).  kind: "stem" (1 x 1, no activation),
 # "dense" (LeakyReLU 0.2 / 0.1), "fconv" (BatchNorm + ReLU: the 32 BatchNorms that ARE applied), "q", "k", "v", "proj" (the attention's
