@@ -483,6 +483,25 @@ int paif_sr_attention_split_fwd(const float* q, const float* kv, float* out, flo
 int paif_sr_attention_bf16x3_fwd(const float* q, const float* kv, float* out, float* lse, int B, int N, int Nk, int C, int heads,
                           paif_stream_t stream);
 
+/* Flash self-attention of the SelAttention primitive (operations_m.py:31-61, Attention inside SelfPath; csrc/attention_full.hip):
+ * qkv [B,N,192*heads] exactly as the to_qkv GEMM writes it (q | k | v column blocks at 0 / 64*heads / 128*heads, head hd at 64*hd in
+ * each; head dim 64), out [B,N,64*heads] = softmax(q k^T * 64^-0.5) v per (batch, head) over all N keys, lse (optional) [B,heads,N].
+ * Online softmax over 64-key tiles, nothing of size N^2; K and V are split into fp16 pairs once per call into `workspace`
+ * (paif_self_attention_workspace_bytes, 16-byte aligned; 0 = shape not built).  fp16 pairs: q, k, v must lie inside fp16's exponent
+ * range.  Asynchronous on `stream`, allocates nothing, capture-safe.  PAIF_ENOSUP: B or heads > 65535, N > 2^30. */
+size_t paif_self_attention_workspace_bytes(int B, int N, int heads);
+int paif_self_attention_fwd(const float* qkv, float* out, float* lse, void* workspace, int B, int N, int heads,
+                            paif_stream_t stream);
+/* Input gradient of paif_self_attention_fwd (operations_m.py:31-61): dqkv [B,N,192*heads] in the layout of qkv (every element written)
+ * from dout [B,N,64*heads] and the saved lse.  P is recomputed from q, k and lse.  Two kernels on the exact fp32 MFMA: the first owns
+ * queries, sweeps the keys, and leaves dq plus, in `workspace` (paif_self_attention_bwd_workspace_bytes), each query's delta = sum_j P dP
+ * and lse renormalised by log sum_j P -- both formed from the recomputed P itself, so they are consistent with it whatever rounding the
+ * forward's out and lse carry; the second owns keys, sweeps the queries, reads those two and leaves dk and dv.  `out` is accepted for the
+ * caller's convenience and not read.  No atomics, no partial slabs, no workgroup waiting on another: the same inputs give the same bits. */
+size_t paif_self_attention_bwd_workspace_bytes(int B, int N, int heads);
+int paif_self_attention_bwd_input(const float* qkv, const float* out, const float* dout, const float* lse, float* dqkv,
+                                  void* workspace, int B, int N, int heads, paif_stream_t stream);
+
 /* F.interpolate(mode='bilinear', align_corners=False) of NHWC x [B,IH,IW,C] written into channels
  * [coff, coff+C) of out [B,OH,OW,ldo] -- the head's upsample + torch.cat (core/segformer_head.py:66-77). */
 int paif_resize_bilinear_into_fwd(const float* x, float* out, int B, int IH, int IW, int C, int OH, int OW, int ldo,

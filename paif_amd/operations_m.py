@@ -691,8 +691,109 @@ class spatial_attn_layer(nn.Module):
             return ops.to_nchw_view(ops.spa1(xh, torch.zeros_like(xh), self.spatial.conv.weight, k, one))
 
 
-def _selfpath(*a, **k):
-    raise NotImplementedError("SelAttention/SelfPath is unreachable from MixedOp in the reference (SURVEY.md 8(a) F4)")
+class Attention(nn.Module):
+    """operations_m.py:31-61: to_qkv -> softmax(q k^T * dim_head^-0.5) v per head over all N tokens -> to_out.  Parameter holder inside
+    SelfPath; the stand-alone call is inference only.  Built: dim 32, dim_head 64, dropout 0, any heads >= 1."""
+
+    def __init__(self, dim, heads=8, dim_head=64, dropout=0.):
+        super().__init__()
+        if dim != 32:
+            raise NotImplementedError("Attention(dim=%r): the HIP path is built for dim = 32 (the search space's channel width)" % (dim,))
+        if not isinstance(heads, int) or heads < 1:
+            raise NotImplementedError("Attention(heads=%r): heads must be an integer >= 1" % (heads,))
+        if dim_head != 64:
+            raise NotImplementedError("Attention(dim_head=%r): the flash kernel is built for dim_head = 64" % (dim_head,))
+        if dropout != 0:
+            raise NotImplementedError("Attention(dropout=%r): only dropout = 0 is built (the reference never sets another)" % (dropout,))
+        inner_dim = dim_head * heads
+        self.heads = heads
+        self.scale = dim_head ** -0.5
+        self.attend = nn.Softmax(dim=-1)
+        self.dropout = nn.Dropout(dropout)
+        self.to_qkv = LinearParams(dim, inner_dim * 3, bias=False)
+        self.to_out = nn.Sequential(LinearParams(inner_dim, dim), nn.Dropout(dropout))    # project_out is always true at dim 32
+
+    def forward(self, x):
+        """x [B,N,32] -> [B,N,32] (operations_m.py:50-61).  Inference only; inside SelfPath the same launches run on the tape."""
+        ops.require_no_grad(x)
+        with torch.no_grad():
+            return self.forward_tokens(x.contiguous())[0]
+
+    def forward_tokens(self, tok, want_lse=False):
+        qkv = ops.gemm(tok, self.to_qkv.weight)
+        o = ops.self_attention(qkv, self.heads, want_lse=want_lse)
+        o, lse = o if want_lse else (o, None)
+        return ops.gemm(o, self.to_out[0].weight, shift=self.to_out[0].bias), qkv, o, lse
+
+
+_SELFPATH_NO_WGRAD = ("SelfPath: parameter gradients (training the SelAttention primitive) are not built -- freeze the parameters "
+                      "(requires_grad_(False)), or run under ops.no_param_grads() / torch.no_grad() for input gradients")
+
+
+class SelfPath(_HipOp):
+    """operations_m.py:90-112 ('SelAttention_<heads>_<d>', the dilation field is ignored):
+    r = PReLU(conv(x)); v1 = Attention(r as [B, H*W, 32]); out = PReLU(conv2(LayerNorm(v1) as [B,32,H,W])), ONE PReLU slope.
+    The maps inside the op are fp32 in every storage mode (a 16-bit input map is cast on entry, the output cast back); the attention
+    core has one arithmetic of its own (csrc/attention_full.hip).  Input gradients only."""
+
+    def __init__(self, dim, reduction=1, num_heads=8, norm_layer=nn.LayerNorm):
+        super().__init__()
+        if dim != 32:
+            raise NotImplementedError("SelfPath(dim=%r): the HIP kernels are built for the 32-channel maps of the search space" % (dim,))
+        if reduction != 1:
+            raise NotImplementedError("SelfPath(reduction=%r): only reduction = 1 is built (the reference never sets another)" % (reduction,))
+        if not isinstance(num_heads, int) or num_heads < 1:
+            raise NotImplementedError("SelfPath(num_heads=%r): num_heads must be an integer >= 1" % (num_heads,))
+        if norm_layer is not nn.LayerNorm:
+            raise NotImplementedError("SelfPath(norm_layer=%r): only nn.LayerNorm is built" % (norm_layer,))
+        self.conv = Conv2dParams(dim, dim, kernel_size=3, stride=1, padding=1, bias=True)
+        self.conv2 = Conv2dParams(dim, dim, kernel_size=3, stride=1, padding=1, bias=True)
+        self.act1 = nn.ReLU(inplace=True)       # constructed and never applied in the reference either
+        self.cross_attn = Attention(dim // reduction, heads=num_heads)
+        self.norm1 = LayerNormParams(dim)
+        self.prelu = PReLUParams()
+
+    def _wpk(self, name, conv):
+        # fp32 maps in every storage mode: never the fp16-storage pack
+        return self._packs.get(name, [conv.weight], lambda: ops.pack_conv_weight(conv.weight, 1, 32, 3, precision=ops.CONFIG["conv_precision"]))
+
+    def _dgrad_w(self, name, w, coff=0, cs=32):
+        return self._packs.get("dg_" + name, [w], lambda: ops.pack_conv_dgrad_weight(w, coff, cs, precision=ops.CONFIG["conv_precision"]))
+
+    def forward_nhwc(self, x, res=(), tape=None):
+        a = self.prelu.weight
+        if tape is not None:
+            if ops.taping_wgrad():
+                raise NotImplementedError(_SELFPATH_NO_WGRAD)
+            check_positive_slope(a, "SelfPath")      # the reverse pass reads conv's PReLU branch off its output
+        in_dt = x.dtype
+        x = ops.cast_storage(x, torch.float32)
+        B, H, W, C = x.shape
+        kw = dict(act=ops.ACT_PRELU, prelu=a)
+        r = ops.conv2d([x], self._wpk("w1", self.conv), 3, 1, shift=self.conv.bias, **kw)
+        v1, qkv, o, lse = self.cross_attn.forward_tokens(r.view(B, H * W, C), want_lse=tape is not None)
+        ln = ops.layernorm(v1, self.norm1.weight, self.norm1.bias, self.norm1.eps).view(B, H, W, C)
+        res = tuple(ops.cast_storage(m, torch.float32) for m in res if m is not None)     # added AFTER the last PReLU (conv epilogue order)
+        if tape is None:
+            y = ops.conv2d([ln], self._wpk("w2", self.conv2), 3, 1, shift=self.conv2.bias, res=res, **kw)
+        else:
+            y, z2 = ops.conv2d([ln], self._wpk("w2", self.conv2), 3, 1, shift=self.conv2.bias, res=res, want_aux=True, **kw)
+            tape.append(dict(r=r, qkv=qkv, lse=lse, v1=v1, z2=z2))      # (the attention output is not kept: the reverse kernels do not read it)
+        return ops.cast_storage(y, in_dt)
+
+    def backward_nhwc(self, g, t, wgrad=False):
+        if wgrad:
+            raise NotImplementedError(_SELFPATH_NO_WGRAD)
+        a = self.prelu.weight
+        at = self.cross_attn
+        B, H, W, C = g.shape
+        d_ln = ops.conv2d([g], self._dgrad_w("c2", self.conv2.weight), 3, 1, in_act=ops.IN_DPRELU, in_aux=t["z2"], in_prelu=a)
+        d_v1 = ops.layernorm_bwd(t["v1"], self.norm1.weight, d_ln.view(B, H * W, C), self.norm1.eps)
+        wo, wq = at.to_out[0].weight, at.to_qkv.weight
+        d_o = ops.gemm(d_v1, self._packs.get("outT", [wo], lambda: ops.transpose_pad(wo)))
+        dqkv = ops.self_attention_bwd(t["qkv"], None, d_o, t["lse"], at.heads)
+        d_tok = ops.gemm(dqkv, self._packs.get("qkvT", [wq], lambda: ops.transpose_pad(wq)))
+        return ops.conv2d([d_tok.view(B, H, W, C)], self._dgrad_w("c1", self.conv.weight), 3, 1, in_act=ops.IN_DPRELU, in_aux=t["r"], in_prelu=a)
 
 
 # operations_m.py:9-18
@@ -703,5 +804,5 @@ OPS = {
     'SPAattention': lambda C, kernel, dialtion, affine: Spatial_BasicBlock(C, C, kernel, dialtion),
     'DilConv': lambda C, kernel, dialtion, affine: DilConv(C, C, kernel, dialtion),
     'SepConv': lambda C, kernel, dialtion, affine: SepConv(C, C, kernel, 1, kernel // 2),
-    'SelAttention': lambda C, kernel, dialtion, affine: _selfpath(),
+    'SelAttention': lambda C, kernel, dialtion, affine: SelfPath(dim=C, num_heads=kernel),
 }

@@ -447,6 +447,15 @@ class KernelTimer:
         self._events.append(ev)
         return ev
 
+    def mark(self):
+        """A timing event on the current stream, whatever the tag predicate says (tools that time a span of launches of their own)."""
+        return self._record()
+
+    @classmethod
+    def elapsed_ms(cls, e0, e1):
+        """Milliseconds between two mark()s; call after a synchronize."""
+        return cls._elapsed(e0, e1)
+
     @staticmethod
     def _elapsed(e0, e1):
         if isinstance(e0, torch.cuda.Event):
@@ -2117,6 +2126,52 @@ def sr_attention(q, kv, heads, want_lse=False):
     if e0 is not None:
         TIMER.stop(tag, e0, 4 * B * N * Nk * C, 4 * (2 * B * N * C + 2 * B * Nk * C))
     return (out, lse) if want_lse else out
+
+
+def _self_attention_check(qkv, heads):
+    _p(qkv)
+    if qkv.dim() != 3 or heads < 1 or qkv.shape[-1] != 192 * heads:
+        raise ValueError("self_attention: qkv must be [B, N, 192 * heads] (head dim 64), got %s for heads=%d" % (tuple(qkv.shape), heads))
+    return qkv.shape[0], qkv.shape[1]
+
+
+def self_attention(qkv, heads, want_lse=False):
+    """SelfPath's attention core (operations_m.py:31-61) on the to_qkv GEMM's output as it stands: qkv [B,N,192*heads] (q | k | v column
+    blocks, head hd at 64*hd in each) -> out [B,N,64*heads] (and lse [B,heads,N] for the reverse pass).  Flash form: no N x N tensor."""
+    B, N = _self_attention_check(qkv, heads)
+    L = lib()
+    nws = L.paif_self_attention_workspace_bytes(B, N, heads)
+    if nws == 0:
+        raise NotImplementedError("self_attention: B=%d N=%d heads=%d is not built" % (B, N, heads))
+    ws = torch.empty(nws, device=qkv.device, dtype=torch.uint8)
+    out = torch.empty((B, N, 64 * heads), device=qkv.device, dtype=torch.float32)
+    lse = torch.empty((B, heads, N), device=qkv.device, dtype=torch.float32) if want_lse else None
+    tag = "self_attention_f16x3"
+    e0 = TIMER.start(tag) if TIMER is not None else None
+    _lib.check(L.paif_self_attention_fwd(_p(qkv), _p(out), _p(lse), ctypes.c_void_p(ws.data_ptr()), B, N, heads, _stream()), "self_attention")
+    if e0 is not None:
+        TIMER.stop(tag, e0, 4 * B * heads * N * N * 64, 4 * B * N * 256 * heads)
+    return (out, lse) if want_lse else out
+
+
+def self_attention_bwd(qkv, out, dout, lse, heads):
+    """d(qkv) [B,N,192*heads] of self_attention from d(out) and the saved lse.  `out` may be None: the kernels do not read it (they form
+    delta from the recomputed P), so a caller need not keep it.  Deterministic (no atomics)."""
+    B, N = _self_attention_check(qkv, heads)
+    L = lib()
+    nws = L.paif_self_attention_bwd_workspace_bytes(B, N, heads)
+    if nws == 0:
+        raise NotImplementedError("self_attention_bwd: B=%d N=%d heads=%d is not built" % (B, N, heads))
+    assert tuple(dout.shape) == (B, N, 64 * heads) and tuple(lse.shape) == (B, heads, N) and (out is None or tuple(out.shape) == tuple(dout.shape))
+    ws = torch.empty(nws, device=qkv.device, dtype=torch.uint8)
+    dqkv = torch.empty_like(qkv)
+    tag = "self_attention_bwd_f32"
+    e0 = TIMER.start(tag) if TIMER is not None else None
+    _lib.check(L.paif_self_attention_bwd_input(_p(qkv), _p(out), _p(dout.contiguous()), _p(lse), _p(dqkv), ctypes.c_void_p(ws.data_ptr()),
+                                               B, N, heads, _stream()), "self_attention_bwd")
+    if e0 is not None:
+        TIMER.stop(tag, e0, 16 * B * heads * N * N * 64, 4 * B * N * (192 + 192 + 64) * heads)      # eight N x N x 64 products
+    return dqkv
 
 
 def resize_bilinear_into(x, out, coff):

@@ -138,6 +138,22 @@ def load_formula_weights(module, salt=0, strict=True, head=None):
     return module
 
 
+def selfpath_shapes(heads):
+    """The ten state_dict entries of SelfPath(dim=32, num_heads=heads) (reference operations_m.py:90-112), in module order."""
+    return {"conv.weight": (32, 32, 3, 3), "conv.bias": (32,), "conv2.weight": (32, 32, 3, 3), "conv2.bias": (32,),
+            "cross_attn.to_qkv.weight": (192 * heads, 32), "cross_attn.to_out.0.weight": (32, 64 * heads),
+            "cross_attn.to_out.0.bias": (32,), "norm1.weight": (32,), "norm1.bias": (32,), "prelu.weight": (1,)}
+
+
+def selfpath_state_dict(heads, gain):
+    """key -> float32 numpy array: what load_formula_weights(MixedOp(32, 'SelAttention_<heads>_1'), salt=13) gives its `_op`, with the q and
+    k rows of to_qkv.weight (the first 128 * heads) times `gain` -- the bare formula weights leave the softmax flat (max p ~ 1 / N), so
+    the fixtures of tools/make_golden_selfpath.py store one calibrated gain per head count."""
+    sd = {k: formula_tensor("_op." + k, s, 13) for k, s in selfpath_shapes(heads).items()}
+    sd["cross_attn.to_qkv.weight"][:128 * heads] *= np.float32(gain)
+    return sd
+
+
 # The ten convs of the U2Fusion baseline (reference fusion_model/U2Fusion.py:102-118) as (state_dict prefix, out channels, in channels):
 # its 658,728 weights would not fit a committed fixture, so the fixtures store one fp32 scale per conv and one shift of the last bias.
 U2FUSION_CONVS = ((("conv_1.0", 44, 2),) + tuple(("dense_layers.%d.conv.0" % i, 44, 44 * (i + 1)) for i in range(5))
