@@ -342,11 +342,6 @@ inline unsigned blocks(size_t threads) { return (unsigned)((threads + 255) / 256
 
 }  // namespace
 
-#define BFF_SHAPE(name)                                                                                      \
-  PAIF_REQUIRE(B >= 1 && H >= 1 && W >= 1, PAIF_EINVAL, name ": bad shape %d x %d x %d", B, H, W);            \
-  PAIF_REQUIRE((size_t)B* H* W < ((size_t)1 << 26), PAIF_EINVAL, name ": more than 2^26 pixels");             \
-  const size_t n = (size_t)B * H * W;                                                                        \
-  (void)n
 #define BFF_CH(name, C, cs) \
   PAIF_REQUIRE((C) >= 4 && (C) % 4 == 0 && (cs) >= (C) && (cs) % 4 == 0, PAIF_EINVAL, name ": %d channels at stride %d", (int)(C), (int)(cs))
 
@@ -372,7 +367,7 @@ extern "C" int paif_bffusion_conv(const float* wpk, const float* bias, float slo
   PAIF_REQUIRE(K >= 16 && K % 16 == 0 && in_cs >= K && in_cs % 4 == 0 && M >= 16 && M % 16 == 0 && out_cs >= M && out_cs % 4 == 0, PAIF_EINVAL,
                "bffusion_conv: K = %d at stride %d, M = %d at stride %d", K, in_cs, M, out_cs);
   PAIF_REQUIRE((epi == EPI_ACT) == (bias != nullptr), PAIF_EINVAL, "bffusion_conv: the activation epilogue, and only it, takes a bias");
-  BFF_SHAPE("bffusion_conv");
+  PAIF_SLAB_SHAPE("bffusion_conv", 1, "", 26);
   PAIF_REQUIRE(refl == REFL_NONE || (H >= 2 && W >= 2), PAIF_EINVAL, "bffusion_conv: reflection padding needs H, W >= 2");
   const int ring = refl == REFL_RING ? 2 : 0;
   const int tx = (W + ring + DT - 1) / DT, ty = (H + ring + DT - 1) / DT;
@@ -400,7 +395,7 @@ extern "C" int paif_bffusion_fold(const float* ring, int M, int n_store, float* 
   PAIF_REQUIRE(ring && dst, PAIF_EINVAL, "bffusion_fold: null pointer");
   BFF_CH("bffusion_fold", M, dst_cs);
   PAIF_REQUIRE(n_store >= 0 && n_store <= M && n_store % 4 == 0, PAIF_EINVAL, "bffusion_fold: n_store %d of %d", n_store, M);
-  BFF_SHAPE("bffusion_fold");
+  PAIF_SLAB_SHAPE("bffusion_fold", 1, "", 26);
   PAIF_REQUIRE(H >= 2 && W >= 2, PAIF_EINVAL, "bffusion_fold: reflection padding needs H, W >= 2");
   hipLaunchKernelGGL(fold_k, dim3(blocks(n * (M / 4))), dim3(256), 0, paif::as_stream(stream), ring, M, n_store, dst, dst_cs, H, W, n);
   PAIF_LAUNCH_CHECK("bffusion_fold");
@@ -411,7 +406,7 @@ extern "C" int paif_bffusion_stem_fwd(const float* x, size_t sb, const float* w,
                                       paif_stream_t stream) {
   PAIF_REQUIRE(x && w && bias && out, PAIF_EINVAL, "bffusion_stem_fwd: null pointer");
   BFF_CH("bffusion_stem_fwd", 16, out_cs);
-  BFF_SHAPE("bffusion_stem_fwd");
+  PAIF_SLAB_SHAPE("bffusion_stem_fwd", 1, "", 26);
   PAIF_REQUIRE((size_t)H * W <= sb, PAIF_EINVAL, "bffusion_stem_fwd: batch stride smaller than a plane");
   hipLaunchKernelGGL(stem_fwd_k, dim3(blocks(n * 4)), dim3(256), 0, paif::as_stream(stream), x, sb, w, bias, out, out_cs, (size_t)H * W, n);
   PAIF_LAUNCH_CHECK("bffusion_stem_fwd");
@@ -421,7 +416,7 @@ extern "C" int paif_bffusion_stem_fwd(const float* x, size_t sb, const float* w,
 extern "C" int paif_bffusion_stem_bwd(const float* w, const float* d, int d_cs, float* d_x, int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(w && d && d_x, PAIF_EINVAL, "bffusion_stem_bwd: null pointer");
   BFF_CH("bffusion_stem_bwd", 16, d_cs);
-  BFF_SHAPE("bffusion_stem_bwd");
+  PAIF_SLAB_SHAPE("bffusion_stem_bwd", 1, "", 26);
   hipLaunchKernelGGL(stem_bwd_k, dim3(blocks(n)), dim3(256), 0, paif::as_stream(stream), w, d, d_cs, d_x, n);
   PAIF_LAUNCH_CHECK("bffusion_stem_bwd");
   return 0;
@@ -431,7 +426,7 @@ extern "C" int paif_bffusion_head_fwd(const float* w, const float* bias, const f
                                       paif_stream_t stream) {
   PAIF_REQUIRE(w && bias && in && fused, PAIF_EINVAL, "bffusion_head_fwd: null pointer");
   BFF_CH("bffusion_head_fwd", 16, in_cs);
-  BFF_SHAPE("bffusion_head_fwd");
+  PAIF_SLAB_SHAPE("bffusion_head_fwd", 1, "", 26);
   hipLaunchKernelGGL(head_fwd_k, dim3(blocks(n)), dim3(256), 0, paif::as_stream(stream), w, bias, in, in_cs, fused, n);
   PAIF_LAUNCH_CHECK("bffusion_head_fwd");
   return 0;
@@ -441,7 +436,7 @@ extern "C" int paif_bffusion_head_bwd(const float* w, const float* fused, const 
                                       paif_stream_t stream) {
   PAIF_REQUIRE(w && fused && d_fused && d, PAIF_EINVAL, "bffusion_head_bwd: null pointer");
   BFF_CH("bffusion_head_bwd", 16, d_cs);
-  BFF_SHAPE("bffusion_head_bwd");
+  PAIF_SLAB_SHAPE("bffusion_head_bwd", 1, "", 26);
   hipLaunchKernelGGL(head_bwd_k, dim3(blocks(n * 4)), dim3(256), 0, paif::as_stream(stream), w, fused, d_fused, d, d_cs, n);
   PAIF_LAUNCH_CHECK("bffusion_head_bwd");
   return 0;
@@ -452,7 +447,7 @@ extern "C" int paif_bffusion_pool_fwd(const float* in, int in_cs, int C, float* 
   PAIF_REQUIRE(in && out, PAIF_EINVAL, "bffusion_pool_fwd: null pointer");
   BFF_CH("bffusion_pool_fwd", C, in_cs);
   BFF_CH("bffusion_pool_fwd", C, out_cs);
-  BFF_SHAPE("bffusion_pool_fwd");
+  PAIF_SLAB_SHAPE("bffusion_pool_fwd", 1, "", 26);
   PAIF_REQUIRE(H >= 2 && W >= 2, PAIF_EINVAL, "bffusion_pool_fwd: a 2 x 2 window needs H, W >= 2");
   const int Hp = H / 2, Wp = W / 2;
   const size_t np = (size_t)B * Hp * Wp;
@@ -469,7 +464,7 @@ extern "C" int paif_bffusion_pool_bwd(const float* in, int in_cs, int C, const f
   BFF_CH("bffusion_pool_bwd", C, in_cs);
   BFF_CH("bffusion_pool_bwd", C, dp_cs);
   BFF_CH("bffusion_pool_bwd", C, din_cs);
-  BFF_SHAPE("bffusion_pool_bwd");
+  PAIF_SLAB_SHAPE("bffusion_pool_bwd", 1, "", 26);
   PAIF_REQUIRE(H >= 2 && W >= 2, PAIF_EINVAL, "bffusion_pool_bwd: a 2 x 2 window needs H, W >= 2");
   hipLaunchKernelGGL(pool_bwd_k, dim3(blocks(n * C)), dim3(256), 0, paif::as_stream(stream), in, in_cs, C, H, W, d_pooled, dp_cs, H / 2, W / 2, d_in,
                      din_cs, n);
@@ -482,7 +477,7 @@ extern "C" int paif_bffusion_up_fwd(const float* src, int src_cs, int C, float* 
   PAIF_REQUIRE(src && dst, PAIF_EINVAL, "bffusion_up_fwd: null pointer");
   BFF_CH("bffusion_up_fwd", C, src_cs);
   BFF_CH("bffusion_up_fwd", C, dst_cs);
-  BFF_SHAPE("bffusion_up_fwd");
+  PAIF_SLAB_SHAPE("bffusion_up_fwd", 1, "", 26);
   PAIF_REQUIRE(H >= 2 && W >= 2, PAIF_EINVAL, "bffusion_up_fwd: the destination needs H, W >= 2");
   hipLaunchKernelGGL(up_fwd_k, dim3(blocks(n * (C / 4))), dim3(256), 0, paif::as_stream(stream), src, src_cs, C, H / 2, W / 2, dst, dst_cs, H, W, n);
   PAIF_LAUNCH_CHECK("bffusion_up_fwd");
@@ -493,7 +488,7 @@ extern "C" int paif_bffusion_up_bwd(const float* d_dst, int dd_cs, int C, float*
   PAIF_REQUIRE(d_dst && d_src, PAIF_EINVAL, "bffusion_up_bwd: null pointer");
   BFF_CH("bffusion_up_bwd", C, dd_cs);
   BFF_CH("bffusion_up_bwd", C, ds_cs);
-  BFF_SHAPE("bffusion_up_bwd");
+  PAIF_SLAB_SHAPE("bffusion_up_bwd", 1, "", 26);
   PAIF_REQUIRE(H >= 2 && W >= 2, PAIF_EINVAL, "bffusion_up_bwd: the destination needs H, W >= 2");
   const int Hs = H / 2, Ws = W / 2;
   const size_t ns = (size_t)B * Hs * Ws;
@@ -511,7 +506,7 @@ extern "C" int paif_bffusion_gate_fwd(const float* skip_a, int sa_cs, const floa
   BFF_CH("bffusion_gate_fwd", C, sa_cs);
   BFF_CH("bffusion_gate_fwd", C, sb_cs);
   BFF_CH("bffusion_gate_fwd", C, out_cs);
-  BFF_SHAPE("bffusion_gate_fwd");
+  PAIF_SLAB_SHAPE("bffusion_gate_fwd", 1, "", 26);
   hipLaunchKernelGGL(gate_fwd_k, dim3(blocks(n * (C / 4))), dim3(256), 0, paif::as_stream(stream), skip_a, sa_cs, x_a, skip_b, sb_cs, x_b, C, out, out_cs,
                      n);
   PAIF_LAUNCH_CHECK("bffusion_gate_fwd");
@@ -523,7 +518,7 @@ extern "C" int paif_bffusion_gate_bwd(const float* d_fused, int df_cs, const flo
   PAIF_REQUIRE(d_fused && skip && x && d_x && d_skip, PAIF_EINVAL, "bffusion_gate_bwd: null pointer");
   BFF_CH("bffusion_gate_bwd", C, df_cs);
   BFF_CH("bffusion_gate_bwd", C, skip_cs);
-  BFF_SHAPE("bffusion_gate_bwd");
+  PAIF_SLAB_SHAPE("bffusion_gate_bwd", 1, "", 26);
   hipLaunchKernelGGL(gate_bwd_k, dim3(blocks(n * (C / 4))), dim3(256), 0, paif::as_stream(stream), d_fused, df_cs, skip, skip_cs, x, C, d_x, d_skip, n);
   PAIF_LAUNCH_CHECK("bffusion_gate_bwd");
   return 0;
@@ -533,7 +528,7 @@ extern "C" int paif_bffusion_ln_fwd(const float* y, const float* gamma, const fl
                                     paif_stream_t stream) {
   PAIF_REQUIRE(y && gamma && beta && z && y != z, PAIF_EINVAL, "bffusion_ln_fwd: null or aliased pointer");
   PAIF_REQUIRE(C >= 1 && eps >= 0.f, PAIF_EINVAL, "bffusion_ln_fwd: C = %d, eps = %g", C, eps);
-  BFF_SHAPE("bffusion_ln_fwd");
+  PAIF_SLAB_SHAPE("bffusion_ln_fwd", 1, "", 26);
   hipLaunchKernelGGL(ln_fwd_k, dim3(blocks(n)), dim3(256), 0, paif::as_stream(stream), y, gamma, beta, eps, C, z, n);
   PAIF_LAUNCH_CHECK("bffusion_ln_fwd");
   return 0;
@@ -543,7 +538,7 @@ extern "C" int paif_bffusion_ln_bwd(const float* y, const float* gamma, float ep
                                     paif_stream_t stream) {
   PAIF_REQUIRE(y && gamma && d_z && d_y && d_y != y && d_y != d_z, PAIF_EINVAL, "bffusion_ln_bwd: null or aliased pointer");
   PAIF_REQUIRE(C >= 1 && eps >= 0.f, PAIF_EINVAL, "bffusion_ln_bwd: C = %d, eps = %g", C, eps);
-  BFF_SHAPE("bffusion_ln_bwd");
+  PAIF_SLAB_SHAPE("bffusion_ln_bwd", 1, "", 26);
   hipLaunchKernelGGL(ln_bwd_k, dim3(blocks(n)), dim3(256), 0, paif::as_stream(stream), y, gamma, eps, C, d_z, d_y, n);
   PAIF_LAUNCH_CHECK("bffusion_ln_bwd");
   return 0;
@@ -561,7 +556,7 @@ extern "C" int paif_bffusion_ctx_partial(const float* a, int a_cs, const float* 
                                          paif_stream_t stream) {
   PAIF_REQUIRE(a && b && partial, PAIF_EINVAL, "bffusion_ctx_partial: null pointer");
   PAIF_REQUIRE(a_cs >= dim && b_cs >= dim, PAIF_EINVAL, "bffusion_ctx_partial: stride below dim");
-  BFF_SHAPE("bffusion_ctx_partial");
+  PAIF_SLAB_SHAPE("bffusion_ctx_partial", 1, "", 26);
   BFF_HEADS("bffusion_ctx_partial");
   PAIF_REQUIRE(B <= 65535, PAIF_EINVAL, "bffusion_ctx_partial: batch above 65535");
   hipLaunchKernelGGL(ctx_partial_k, dim3((unsigned)chunks, (unsigned)B), dim3(256), 0, paif::as_stream(stream), a, a_cs, b, b_cs, dim, d, H * W, chunks,
@@ -572,7 +567,7 @@ extern "C" int paif_bffusion_ctx_partial(const float* a, int a_cs, const float* 
 
 extern "C" int paif_bffusion_ctx_softmax(const double* partial, int dim, int d, float scale, float* ctx, int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(partial && ctx, PAIF_EINVAL, "bffusion_ctx_softmax: null pointer");
-  BFF_SHAPE("bffusion_ctx_softmax");
+  PAIF_SLAB_SHAPE("bffusion_ctx_softmax", 1, "", 26);
   BFF_HEADS("bffusion_ctx_softmax");
   hipLaunchKernelGGL(ctx_softmax_k, dim3(blocks((size_t)B * dim)), dim3(256), 0, paif::as_stream(stream), partial, chunks, dim, d, scale, ctx, B * dim);
   PAIF_LAUNCH_CHECK("bffusion_ctx_softmax");
@@ -582,7 +577,7 @@ extern "C" int paif_bffusion_ctx_softmax(const double* partial, int dim, int d, 
 extern "C" int paif_bffusion_ctx_softmax_bwd(const double* partial, int dim, int d, float scale, const float* ctx, float* d_s, int B, int H, int W,
                                              paif_stream_t stream) {
   PAIF_REQUIRE(partial && ctx && d_s, PAIF_EINVAL, "bffusion_ctx_softmax_bwd: null pointer");
-  BFF_SHAPE("bffusion_ctx_softmax_bwd");
+  PAIF_SLAB_SHAPE("bffusion_ctx_softmax_bwd", 1, "", 26);
   BFF_HEADS("bffusion_ctx_softmax_bwd");
   hipLaunchKernelGGL(ctx_softmax_bwd_k, dim3(blocks((size_t)B * dim)), dim3(256), 0, paif::as_stream(stream), partial, chunks, dim, d, scale, ctx, d_s,
                      B * dim);
@@ -592,7 +587,7 @@ extern "C" int paif_bffusion_ctx_softmax_bwd(const double* partial, int dim, int
 
 extern "C" int paif_bffusion_attn_apply_fwd(const float* qkv, const float* ctx, int dim, int d, float* x, int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(qkv && ctx && x, PAIF_EINVAL, "bffusion_attn_apply_fwd: null pointer");
-  BFF_SHAPE("bffusion_attn_apply_fwd");
+  PAIF_SLAB_SHAPE("bffusion_attn_apply_fwd", 1, "", 26);
   BFF_HEADS("bffusion_attn_apply_fwd");
   hipLaunchKernelGGL(attn_apply_fwd_k, dim3(blocks(n * dim)), dim3(256), 0, paif::as_stream(stream), qkv, ctx, dim, d, H * W, x, n);
   PAIF_LAUNCH_CHECK("bffusion_attn_apply_fwd");
@@ -602,7 +597,7 @@ extern "C" int paif_bffusion_attn_apply_fwd(const float* qkv, const float* ctx, 
 extern "C" int paif_bffusion_attn_apply_bwd(const float* qkv, const float* d_x, const float* ctx, const float* d_s, int dim, int d, float* d_qkv, int B,
                                             int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(qkv && d_x && ctx && d_s && d_qkv, PAIF_EINVAL, "bffusion_attn_apply_bwd: null pointer");
-  BFF_SHAPE("bffusion_attn_apply_bwd");
+  PAIF_SLAB_SHAPE("bffusion_attn_apply_bwd", 1, "", 26);
   BFF_HEADS("bffusion_attn_apply_bwd");
   hipLaunchKernelGGL(attn_apply_bwd_k, dim3(blocks(n * dim)), dim3(256), 0, paif::as_stream(stream), qkv, d_x, ctx, d_s, dim, d, H * W, d_qkv, n);
   PAIF_LAUNCH_CHECK("bffusion_attn_apply_bwd");

@@ -1,5 +1,5 @@
-// The SLAB CONV: an exact-fp32 implicit GEMM on v_mfma_f32_16x16x4_f32 over a slice of an NHWC concat slab -- the conv_k of u2fusion.hip,
-// generalised by template / argument (u2fusion.hip keeps its own copy for now):
+// The SLAB CONV: an exact-fp32 implicit GEMM on v_mfma_f32_16x16x4_f32 over a slice of an NHWC concat slab, shaped by template / argument
+// (u2fusion.hip, seafusion.hip, didfuse.hip, bffusion.hip and drdb.hip all run on it; their shared host scaffolding is at the end):
 //   * TAPS: 9 (3 x 3, zero pad 1) or 1 (1 x 1: no halo is staged);
 //   * MB in {1, 2, 3, 4} blocks of 16 output channels per workgroup (plan_for(): a 16-channel output spends no instruction on zeros);
 //   * the LeakyReLU slope is an argument: of the store epilogue (EPI_ACT) or of the input mask (MASK);
@@ -16,7 +16,7 @@
 //     pixel; act(v + b) itself goes to `avg` (the tape of the branch: x + r can equal x in fp32 for a small positive r).
 //   ReLU is LeakyReLU at slope 0, epilogue and mask alike (a negative input stores -0, which every consumer treats as 0).
 // The last five default to what the header did before them: an instantiation that does not name them compiles to the same code.
-// Everything else is conv_k's.  Output CHANNELS on M, 16 PIXELS of one image row on N; the D operand of lane l is channels
+// Output CHANNELS on M, 16 PIXELS of one image row on N; the D operand of lane l is channels
 // 4 (l >> 4) .. + 3 of pixel l & 15, one float4 of the NHWC map, and the B operand of four consecutive instructions is one float4 of the
 // input map.  A workgroup of four waves owns a 16 x 16 pixel tile (four rows per wave) and MB blocks of 16 output channels (blockIdx.y
 // selects the group of MB blocks).  Per CHUNK of 16 input channels it stages the tile (+ halo 1 for 9 taps; what lies outside the image
@@ -255,4 +255,75 @@ void launch_conv4(dim3 grid, hipStream_t s, const ConvArgs& a) {
   hipLaunchKernelGGL((conv_k<9, 4, MASK, EPI, ACT, PAIR, XIN>), grid, dim3(256), 0, s, a);
 }
 
+// ---- host scaffolding of the networks on the slab conv ----------------------------------------------------------------------------------
+inline void pack_ops(const float* w, int co, int n, int off, const Plan& pl, int transposed, float* dst, hipStream_t s) {
+  hipLaunchKernelGGL(pack_ops_k, dim3((unsigned)((pl.floats() + 255) / 256)), dim3(256), 0, s, w, co, n, off, pl, transposed, dst);
+}
+// What every launch fills the same way: the plane, its tiling, the plan's chunks.  Pointers start null, the slope 0, the scales 1: a call
+// site names the pointers, strides, offsets and slope its form reads.
+inline ConvArgs conv_args(const Plan& pl, int H, int W, int tx, int ty) {
+  ConvArgs a{};
+  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
+  return a;
+}
+inline dim3 conv_grid(const Plan& pl, int B, int tx, int ty) { return dim3((unsigned)(tx * ty * B), (unsigned)pl.groups); }
+
+// ---- a 3 x 3, zero pad 1, 32 -> 1 head on the vector unit (U2Fusion's sub.3 with tanh, DRDB's conv21 with PReLU).  hp: the weights
+// [tap 9][ci 32] through the scalar cache, then the bias; tap ascending, channel quad ascending.  One pixel per thread --------------------
+template <int ACT>
+__global__ __launch_bounds__(256) void head32_fwd_k(const float* __restrict__ hp, float slope, const float* __restrict__ in, float* __restrict__ out,
+                                                    int H, int W, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
+  if (i >= n) return;
+  const size_t hw = (size_t)H * W;
+  const int b = (int)(i / hw), y = (int)((i - b * hw) / W), x = (int)(i - b * hw - (size_t)y * W);
+  float s = 0.f;
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    const int gy = y + tap / 3 - 1, gx = x + tap % 3 - 1;
+    if ((unsigned)gy >= (unsigned)H || (unsigned)gx >= (unsigned)W) continue;
+    const float* __restrict__ src = in + ((size_t)b * hw + (size_t)gy * W + gx) * 32;
+    const float* __restrict__ wt = hp + tap * 32;
+#pragma unroll
+    for (int c = 0; c < 32; c += 4) {
+      const float4 v = *reinterpret_cast<const float4*>(src + c);
+      s = fmaf(wt[c], v.x, s), s = fmaf(wt[c + 1], v.y, s), s = fmaf(wt[c + 2], v.z, s), s = fmaf(wt[c + 3], v.w, s);
+    }
+  }
+  out[i] = act_of<ACT>(s + hp[9 * 32], slope);
+}
+// Reverse: dy = g through the activation's derivative off the taped OUTPUT; d_in[p][ci] = sum over tap of W[ci][tap] * dy[p - (tap - centre)].
+// Eight lanes per pixel, one channel quad each; WRITES d_in.
+template <int ACT>
+__global__ __launch_bounds__(256) void head32_bwd_k(const float* __restrict__ hp, float slope, const float* __restrict__ out, const float* __restrict__ g,
+                                                    float* __restrict__ din, int H, int W, size_t n) {
+  const size_t i = (size_t)blockIdx.x * 32 + (threadIdx.x >> 3);
+  const int cq = threadIdx.x & 7;
+  if (i >= n) return;
+  const size_t hw = (size_t)H * W;
+  const int b = (int)(i / hw), y = (int)((i - b * hw) / W), x = (int)(i - b * hw - (size_t)y * W);
+  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
+#pragma unroll
+  for (int tap = 0; tap < 9; ++tap) {
+    const int gy = y - (tap / 3 - 1), gx = x - (tap % 3 - 1);
+    if ((unsigned)gy >= (unsigned)H || (unsigned)gx >= (unsigned)W) continue;
+    const size_t o = (size_t)b * hw + (size_t)gy * W + gx;
+    const float dy = ACT == ACT_TANH ? dtanh(out[o], g[o]) : dleaky(out[o], g[o], slope);
+    const float4 wv = *reinterpret_cast<const float4*>(hp + tap * 32 + 4 * cq);
+    s.x = fmaf(wv.x, dy, s.x), s.y = fmaf(wv.y, dy, s.y), s.z = fmaf(wv.z, dy, s.z), s.w = fmaf(wv.w, dy, s.w);
+  }
+  *reinterpret_cast<float4*>(din + i * 32 + 4 * cq) = s;
+}
+
 }  // namespace paif_slab
+
+// ---- the shape checks of an entry point with B, H, W in scope: an image of at least min_hw x min_hw (`why` is what the message says about
+// a minimum above 1), fewer than 2^cap pixels; defines n = B H W.  PAIF_SLAB_TILES defines the tiling tx, ty of the slab conv ------------
+#define PAIF_SLAB_SHAPE(name, min_hw, why, cap)                                                                    \
+  PAIF_REQUIRE(B >= 1 && H >= min_hw && W >= min_hw, PAIF_EINVAL, name ": bad shape %d x %d x %d" why, B, H, W);     \
+  PAIF_REQUIRE((size_t)B* H* W < ((size_t)1 << cap), PAIF_EINVAL, name ": more than 2^" #cap " pixels");             \
+  const size_t n = (size_t)B * H * W;                                                                              \
+  (void)n
+#define PAIF_SLAB_TILES(name)                                                                                      \
+  const int tx = (W + paif_slab::DT - 1) / paif_slab::DT, ty = (H + paif_slab::DT - 1) / paif_slab::DT;              \
+  PAIF_REQUIRE((size_t)tx* ty* B < ((size_t)1 << 31), PAIF_EINVAL, name ": too many tiles")

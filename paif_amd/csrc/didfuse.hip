@@ -230,10 +230,6 @@ __global__ __launch_bounds__(256) void head_bwd_k(const float* __restrict__ pack
   *reinterpret_cast<float4*>(dd2 + i * DEC + CH + c) = s1;
 }
 
-void pack_ops(const float* w, int co, int n, const Plan& pl, int transposed, float* dst, hipStream_t s) {
-  hipLaunchKernelGGL(pack_ops_k, dim3((unsigned)((pl.floats() + 255) / 256)), dim3(256), 0, s, w, co, n, 0, pl, transposed, dst);
-}
-
 }  // namespace
 
 extern "C" size_t paif_didfuse_pack_floats(void) { return PK_FLOATS; }
@@ -259,20 +255,13 @@ extern "C" int paif_didfuse_pack_conv(const float* w, const float* b, const floa
     hipLaunchKernelGGL(fold_k, dim3((unsigned)((CH * per + 255) / 256)), th, 0, s, w, b, bn_weight, bn_bias, bn_mean, bn_var, eps, CH, per, 0,
                        pack + fold_off(l) + (size_t)row * per, pack + bias_off(l) + row);
     // the operand packs read the layer's whole folded weight: for cov3 | cov4 the later call of the two completes them
-    for (int tr = 0; tr < 2; ++tr) pack_ops(pack + fold_off(l), y.cout, y.cin, plan_of(l, tr != 0), tr, pack + ops_off(l, tr != 0), s);
+    for (int tr = 0; tr < 2; ++tr) pack_ops(pack + fold_off(l), y.cout, y.cin, 0, plan_of(l, tr != 0), tr, pack + ops_off(l, tr != 0), s);
   }
   PAIF_LAUNCH_CHECK("didfuse_pack_conv");
   return 0;
 }
 
-#define DID_SHAPE(name)                                                                                            \
-  PAIF_REQUIRE(B >= 1 && H >= 2 && W >= 2, PAIF_EINVAL, name ": bad shape %d x %d x %d (reflection padding needs H, W >= 2)", B, H, W); \
-  PAIF_REQUIRE((size_t)B* H* W < ((size_t)1 << 31), PAIF_EINVAL, name ": more than 2^31 pixels");                    \
-  const size_t n = (size_t)B * H * W;                                                                              \
-  (void)n
-#define DID_TILES(name)                                                                                            \
-  const int tx = (W + DT - 1) / DT, ty = (H + DT - 1) / DT;                                                        \
-  PAIF_REQUIRE((size_t)tx* ty* B < ((size_t)1 << 31), PAIF_EINVAL, name ": too many tiles")
+#define DID_WHY " (reflection padding needs H, W >= 2)"   // cov1 and cov7 reflect: every entry point refuses a plane they could not take
 
 extern "C" int paif_didfuse_stem_fwd(const float* x, size_t sb, const float* pack, int stream_id, float slope, float* enc, const float* enc0,
                                      float* d2, int B, int H, int W, paif_stream_t stream) {
@@ -281,7 +270,7 @@ extern "C" int paif_didfuse_stem_fwd(const float* x, size_t sb, const float* pac
   PAIF_REQUIRE((stream_id == 1) == (enc0 != nullptr) && (stream_id == 1) == (d2 != nullptr), PAIF_EINVAL,
                "didfuse_stem_fwd: stream 1, and only stream 1, takes stream 0's enc and the slab d2 for the mean");
   PAIF_REQUIRE(enc0 != enc, PAIF_EINVAL, "didfuse_stem_fwd: the two streams' maps must differ");
-  DID_SHAPE("didfuse_stem_fwd");
+  PAIF_SLAB_SHAPE("didfuse_stem_fwd", 2, DID_WHY, 31);
   PAIF_REQUIRE((size_t)H * W <= sb, PAIF_EINVAL, "didfuse_stem_fwd: batch stride smaller than a plane");
   const dim3 grid((unsigned)((n + 15) / 16)), th(256);
   const float* pw = pack + PK_STEM + 640 * stream_id;
@@ -301,22 +290,21 @@ extern "C" int paif_didfuse_conv_fwd(const float* pack, int layer, float slope, 
                "didfuse_conv_fwd: the layers of stream 1, and only they, take stream 0's enc and the slab of the mean");
   PAIF_REQUIRE(!paired || (pair != out && avg != out && (const float*)avg != pair), PAIF_EINVAL,
                "didfuse_conv_fwd: three different maps are expected");
-  DID_SHAPE("didfuse_conv_fwd");
-  DID_TILES("didfuse_conv_fwd");
+  PAIF_SLAB_SHAPE("didfuse_conv_fwd", 2, DID_WHY, 31);
+  PAIF_SLAB_TILES("didfuse_conv_fwd");
   const Layer y = layer_of(layer);
   const Plan pl = plan_of(layer, false);
   const bool wide = layer < 4 && (layer & 1);   // cov3 | cov4
-  ConvArgs a;
-  a.wpk = pack + ops_off(layer, false), a.bias = pack + bias_off(layer), a.bias2 = nullptr, a.mask = nullptr, a.slope = slope, a.out = out;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);
+  a.wpk = pack + ops_off(layer, false), a.bias = pack + bias_off(layer), a.slope = slope, a.out = out;
   if (layer < 4) {
     a.in = in + (wide ? CH : 0), a.in_cs = ENC, a.out_cs = ENC, a.out_off = wide ? 2 * CH : CH;
   } else {
     a.in = in, a.in_cs = DEC, a.out_cs = DEC, a.out_off = 0;
   }
   a.nq = y.cin / 4, a.out_n = y.cout;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
   a.pair = pair, a.avg = avg, a.avg_cs = DEC, a.avg_off = wide ? 0 : CH;   // F_b | F_d fill bd, F_2 is [64, 128) of d1
-  const dim3 grid((unsigned)(tx * ty * B), (unsigned)pl.groups);
+  const dim3 grid = conv_grid(pl, B, tx, ty);
   const hipStream_t s = paif::as_stream(stream);
   if (wide && paired) launch_conv4<false, EPI_ACT, ACT_TANH, true, XIN_PLAIN>(grid, s, a);
   else if (wide) launch_conv4<false, EPI_ACT, ACT_TANH, false, XIN_PLAIN>(grid, s, a);
@@ -328,7 +316,7 @@ extern "C" int paif_didfuse_conv_fwd(const float* pack, int layer, float slope, 
 
 extern "C" int paif_didfuse_head_fwd(const float* pack, const float* d2, float* fused, int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(pack && d2 && fused, PAIF_EINVAL, "didfuse_head_fwd: null pointer");
-  DID_SHAPE("didfuse_head_fwd");
+  PAIF_SLAB_SHAPE("didfuse_head_fwd", 2, DID_WHY, 31);
   hipLaunchKernelGGL(head_fwd_k, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, paif::as_stream(stream), pack, d2, fused, H, W, n);
   PAIF_LAUNCH_CHECK("didfuse_head_fwd");
   return 0;
@@ -337,7 +325,7 @@ extern "C" int paif_didfuse_head_fwd(const float* pack, const float* d2, float* 
 extern "C" int paif_didfuse_head_bwd(const float* pack, const float* fused, const float* d_fused, float* d_d2, int B, int H, int W,
                                      paif_stream_t stream) {
   PAIF_REQUIRE(pack && fused && d_fused && d_d2, PAIF_EINVAL, "didfuse_head_bwd: null pointer");
-  DID_SHAPE("didfuse_head_bwd");
+  PAIF_SLAB_SHAPE("didfuse_head_bwd", 2, DID_WHY, 31);
   hipLaunchKernelGGL(head_bwd_k, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, paif::as_stream(stream), pack, fused, d_fused, d_d2, H, W, n);
   PAIF_LAUNCH_CHECK("didfuse_head_bwd");
   return 0;
@@ -352,15 +340,14 @@ extern "C" int paif_didfuse_conv_bwd(const float* pack, int layer, float slope, 
   PAIF_REQUIRE(cov2 == (d_out == d_in), PAIF_EINVAL, "didfuse_conv_bwd: cov2's transpose works inside dg, every other one from one map to another");
   PAIF_REQUIRE(cov2 == (d_skip != nullptr), PAIF_EINVAL, "didfuse_conv_bwd: cov2's transpose, and only it, takes d_d1 for the mean's transpose");
   PAIF_REQUIRE(d_skip != d_in, PAIF_EINVAL, "didfuse_conv_bwd: d_d1 must not be the map that is written");
-  DID_SHAPE("didfuse_conv_bwd");
-  DID_TILES("didfuse_conv_bwd");
+  PAIF_SLAB_SHAPE("didfuse_conv_bwd", 2, DID_WHY, 31);
+  PAIF_SLAB_TILES("didfuse_conv_bwd");
   const Layer y = layer_of(layer);
   const Plan pl = plan_of(layer, true);
-  ConvArgs a;
-  a.wpk = pack + ops_off(layer, true), a.bias = nullptr, a.bias2 = nullptr, a.slope = slope, a.out = d_in;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);
+  a.wpk = pack + ops_off(layer, true), a.slope = slope, a.out = d_in;
   a.nq = y.cout / 4, a.in_cs = DEC, a.out_cs = DEC, a.out_n = y.cin;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
-  const dim3 grid((unsigned)(tx * ty * B), (unsigned)pl.groups);
+  const dim3 grid = conv_grid(pl, B, tx, ty);
   const hipStream_t s = paif::as_stream(stream);
   if (cov34) {          // d_bd (all 128), tanh' from fB | fD, the mean's 0.5 -> dg[64:128)
     a.in = d_out, a.mask = taped + 2 * CH, a.mask_cs = ENC, a.in_scale = 0.5f, a.out_off = CH;
@@ -380,7 +367,7 @@ extern "C" int paif_didfuse_stem_bwd(const float* pack, int stream_id, float slo
                                      int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(pack && enc && dg && d_d2 && d_x, PAIF_EINVAL, "didfuse_stem_bwd: null pointer");
   PAIF_REQUIRE(stream_id == 0 || stream_id == 1, PAIF_EINVAL, "didfuse_stem_bwd: stream %d is neither 0 (x_over) nor 1 (x_under)", stream_id);
-  DID_SHAPE("didfuse_stem_bwd");
+  PAIF_SLAB_SHAPE("didfuse_stem_bwd", 2, DID_WHY, 31);
   hipLaunchKernelGGL(stem_bwd_k, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, paif::as_stream(stream), pack + PK_STEM + 640 * stream_id, slope, enc,
                      dg, d_d2, d_x, H, W, n);
   PAIF_LAUNCH_CHECK("didfuse_stem_bwd");

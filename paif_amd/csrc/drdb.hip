@@ -63,6 +63,7 @@ __host__ __device__ constexpr size_t ops_off(int l, bool transposed) {   // laye
 }
 constexpr size_t PK_FLOATS = ops_off(13, true);
 static_assert(PK_HEAD_W % 4 == 0 && PK_BIAS % 4 == 0 && PK_OPS % 4 == 0, "float4 loads from the pack stay aligned");
+static_assert(PK_HEAD_B == PK_HEAD_W + 9 * 32, "head32_*_k read the bias behind the weights");
 
 // ---- weight packing -----------------------------------------------------------------------------------------------------------------
 // a vector-unit weight [co][ci][tap] -> [tap][ci][co] (conv1: ci 2, co 64; conv21: ci 32, co 1), and a bias as it is
@@ -135,50 +136,8 @@ __global__ __launch_bounds__(256) void stem_bwd_k(const float* __restrict__ pack
   d_vis[i] = s1;
 }
 
-// ---- conv21: 32 -> 1, bias, PReLU -> f (BEFORE the clamp).  One pixel per thread ----------------------------------------------------------
-__global__ __launch_bounds__(256) void head_fwd_k(const float* __restrict__ pack, float slope, const float* __restrict__ c2, float* __restrict__ f,
-                                                  int H, int W, size_t n) {
-  const size_t i = (size_t)blockIdx.x * 256 + threadIdx.x;
-  if (i >= n) return;
-  const size_t hw = (size_t)H * W;
-  const int b = (int)(i / hw), y = (int)((i - b * hw) / W), x = (int)(i - b * hw - (size_t)y * W);
-  float s = 0.f;
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) {
-    const int gy = y + tap / 3 - 1, gx = x + tap % 3 - 1;
-    if ((unsigned)gy >= (unsigned)H || (unsigned)gx >= (unsigned)W) continue;
-    const float* __restrict__ src = c2 + ((size_t)b * hw + (size_t)gy * W + gx) * 32;
-    const float* __restrict__ wt = pack + PK_HEAD_W + tap * 32;
-#pragma unroll
-    for (int c = 0; c < 32; c += 4) {
-      const float4 v = *reinterpret_cast<const float4*>(src + c);
-      s = fmaf(wt[c], v.x, s), s = fmaf(wt[c + 1], v.y, s), s = fmaf(wt[c + 2], v.z, s), s = fmaf(wt[c + 3], v.w, s);
-    }
-  }
-  f[i] = leaky(s + pack[PK_HEAD_B], slope);
-}
-
-// Reverse: dy = d_f through the PReLU (branch from the taped f); d_c2[p][ci] = sum over tap of W[ci][tap] * dy[p - (tap - centre)].
-// Eight lanes per pixel, one channel quad each; WRITES d_c2.
-__global__ __launch_bounds__(256) void head_bwd_k(const float* __restrict__ pack, float slope, const float* __restrict__ f, const float* __restrict__ df,
-                                                  float* __restrict__ dc2, int H, int W, size_t n) {
-  const size_t i = (size_t)blockIdx.x * 32 + (threadIdx.x >> 3);
-  const int cq = threadIdx.x & 7;
-  if (i >= n) return;
-  const size_t hw = (size_t)H * W;
-  const int b = (int)(i / hw), y = (int)((i - b * hw) / W), x = (int)(i - b * hw - (size_t)y * W);
-  float4 s = make_float4(0.f, 0.f, 0.f, 0.f);
-#pragma unroll
-  for (int tap = 0; tap < 9; ++tap) {
-    const int gy = y - (tap / 3 - 1), gx = x - (tap % 3 - 1);
-    if ((unsigned)gy >= (unsigned)H || (unsigned)gx >= (unsigned)W) continue;
-    const size_t o = (size_t)b * hw + (size_t)gy * W + gx;
-    const float dy = dleaky(f[o], df[o], slope);
-    const float4 wv = *reinterpret_cast<const float4*>(pack + PK_HEAD_W + tap * 32 + 4 * cq);
-    s.x = fmaf(wv.x, dy, s.x), s.y = fmaf(wv.y, dy, s.y), s.z = fmaf(wv.z, dy, s.z), s.w = fmaf(wv.w, dy, s.w);
-  }
-  *reinterpret_cast<float4*>(dc2 + i * 32 + 4 * cq) = s;
-}
+// conv21 (32 -> 1, bias, PReLU -> f, BEFORE the clamp) and its reverse (branch from the taped f) are head32_fwd_k / head32_bwd_k<ACT_LEAKY>
+// of conv_slab.h.
 
 // ---- the residual of a DRDB in reverse: d_slab[0:64] += d_out.  Sixteen lanes per pixel, one channel quad each ---------------------------
 __global__ __launch_bounds__(256) void resid_add_k(const float* __restrict__ d_out, int cs, float* __restrict__ dslab, size_t n) {
@@ -189,10 +148,6 @@ __global__ __launch_bounds__(256) void resid_add_k(const float* __restrict__ d_o
   float4* o = reinterpret_cast<float4*>(dslab + i * SLAB + c);   // owned by this lane
   const float4 u = *o;
   *o = make_float4(u.x + g.x, u.y + g.y, u.z + g.z, u.w + g.w);
-}
-
-void pack_ops(const float* w, int co, int n, const Plan& pl, int transposed, float* dst, hipStream_t s) {
-  hipLaunchKernelGGL(pack_ops_k, dim3((unsigned)((pl.floats() + 255) / 256)), dim3(256), 0, s, w, co, n, 0, pl, transposed, dst);
 }
 
 // the dilation-2 3 x 3 forms
@@ -220,20 +175,12 @@ extern "C" int paif_drdb_pack_conv(const float* w, const float* b, int conv, flo
     const int l = conv - 1;
     const Layer y = layer_of(l);
     hipLaunchKernelGGL(pack_small_k, dim3(1), th, 0, s, (const float*)nullptr, 0, 0, (float*)nullptr, b, y.cout, pack + bias_off(l));
-    for (int tr = 0; tr < 2; ++tr) pack_ops(w, y.cout, y.cin, plan_of(l, tr != 0), tr, pack + ops_off(l, tr != 0), s);
+    for (int tr = 0; tr < 2; ++tr) pack_ops(w, y.cout, y.cin, 0, plan_of(l, tr != 0), tr, pack + ops_off(l, tr != 0), s);
   }
   PAIF_LAUNCH_CHECK("drdb_pack_conv");
   return 0;
 }
 
-#define DRDB_SHAPE(name)                                                                                  \
-  PAIF_REQUIRE(B >= 1 && H >= 1 && W >= 1, PAIF_EINVAL, name ": bad shape %d x %d x %d", B, H, W);          \
-  PAIF_REQUIRE((size_t)B* H* W < ((size_t)1 << 31), PAIF_EINVAL, name ": more than 2^31 pixels");           \
-  const size_t n = (size_t)B * H * W;                                                                       \
-  (void)n
-#define DRDB_TILES(name)                                                                                  \
-  const int tx = (W + DT - 1) / DT, ty = (H + DT - 1) / DT;                                                 \
-  PAIF_REQUIRE((size_t)tx* ty* B < ((size_t)1 << 31), PAIF_EINVAL, name ": too many tiles")
 #define DRDB_BLOCK(name) PAIF_REQUIRE(block == 0 || block == 1, PAIF_EINVAL, name ": block %d is neither 0 (DRDB1) nor 1 (DRDB2)", block)
 #define DRDB_SLOPE(name) PAIF_REQUIRE(slope >= 0.f, PAIF_EINVAL, name ": the PReLU slope %g is negative (the branch is read off the taped output)", (double)slope)
 
@@ -241,7 +188,7 @@ extern "C" int paif_drdb_stem_fwd(const float* ir, size_t sb_ir, const float* vi
                                   int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(ir && vis && pack && slab, PAIF_EINVAL, "drdb_stem_fwd: null pointer");
   DRDB_SLOPE("drdb_stem_fwd");
-  DRDB_SHAPE("drdb_stem_fwd");
+  PAIF_SLAB_SHAPE("drdb_stem_fwd", 1, "", 31);
   PAIF_REQUIRE((size_t)H * W <= sb_ir && (size_t)H * W <= sb_vis, PAIF_EINVAL, "drdb_stem_fwd: batch stride smaller than a plane");
   hipLaunchKernelGGL(stem_fwd_k, dim3((unsigned)((n + 255) / 256), 4), dim3(256), 0, paif::as_stream(stream), ir, sb_ir, vis, sb_vis, pack, slope,
                      slab, H, W, n);
@@ -253,17 +200,16 @@ extern "C" int paif_drdb_dcov_fwd(const float* pack, int block, int k, float* sl
   PAIF_REQUIRE(pack && slab, PAIF_EINVAL, "drdb_dcov_fwd: null pointer");
   DRDB_BLOCK("drdb_dcov_fwd");
   PAIF_REQUIRE(k >= 1 && k <= 5, PAIF_EINVAL, "drdb_dcov_fwd: Dcov%d does not exist", k);
-  DRDB_SHAPE("drdb_dcov_fwd");
-  DRDB_TILES("drdb_dcov_fwd");
+  PAIF_SLAB_SHAPE("drdb_dcov_fwd", 1, "", 31);
+  PAIF_SLAB_TILES("drdb_dcov_fwd");
   const int l = 6 * block + k - 1;
   const Layer y = layer_of(l);
   const Plan pl = plan_of(l, false);
-  ConvArgs a;
-  a.in = slab, a.mask = nullptr, a.out = slab, a.wpk = pack + ops_off(l, false), a.bias = pack + bias_off(l), a.bias2 = nullptr, a.slope = 0.f;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);   // slope 0: ReLU
+  a.in = slab, a.out = slab, a.wpk = pack + ops_off(l, false), a.bias = pack + bias_off(l);
   a.in_cs = SLAB, a.nq = y.cin / 4;
   a.out_cs = SLAB, a.out_off = y.cin, a.out_n = GROW;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
-  launch_dil2<false, EPI_ACT>(pl.MB, dim3((unsigned)(tx * ty * B), (unsigned)pl.groups), paif::as_stream(stream), a);
+  launch_dil2<false, EPI_ACT>(pl.MB, conv_grid(pl, B, tx, ty), paif::as_stream(stream), a);
   PAIF_LAUNCH_CHECK("drdb_dcov_fwd");
   return 0;
 }
@@ -274,16 +220,15 @@ extern "C" int paif_drdb_tail_fwd(const float* pack, int block, const float* sla
   DRDB_BLOCK("drdb_tail_fwd");
   PAIF_REQUIRE(out_cs == SLAB || out_cs == CX, PAIF_EINVAL, "drdb_tail_fwd: the output is a 224-channel slab or a 64-channel map, not %d", out_cs);
   PAIF_REQUIRE(slab != out && slab != r6 && out != r6, PAIF_EINVAL, "drdb_tail_fwd: three different maps are expected");
-  DRDB_SHAPE("drdb_tail_fwd");
-  DRDB_TILES("drdb_tail_fwd");
+  PAIF_SLAB_SHAPE("drdb_tail_fwd", 1, "", 31);
+  PAIF_SLAB_TILES("drdb_tail_fwd");
   const int l = 6 * block + 5;
   const Plan pl = plan_of(l, false);
-  ConvArgs a;
-  a.in = slab, a.mask = nullptr, a.out = out, a.wpk = pack + ops_off(l, false), a.bias = pack + bias_off(l), a.bias2 = nullptr, a.slope = 0.f;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);   // slope 0: ReLU
+  a.in = slab, a.out = out, a.wpk = pack + ops_off(l, false), a.bias = pack + bias_off(l);
   a.in_cs = SLAB, a.nq = SLAB / 4;
   a.out_cs = out_cs, a.out_off = 0, a.out_n = CX;
   a.avg = r6, a.avg_cs = CX, a.avg_off = 0;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
   static_assert(plan_of(5, false).MB == 4 && plan_of(5, false).groups == 1, "64 output channels in one group");
   hipLaunchKernelGGL((conv_k<1, 4, false, EPI_RES>), dim3((unsigned)(tx * ty * B), 1), dim3(256), 0, paif::as_stream(stream), a);
   PAIF_LAUNCH_CHECK("drdb_tail_fwd");
@@ -293,15 +238,14 @@ extern "C" int paif_drdb_tail_fwd(const float* pack, int block, const float* sla
 extern "C" int paif_drdb_conv2_fwd(const float* pack, float slope, const float* in, float* c2, int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(pack && in && c2 && in != c2, PAIF_EINVAL, "drdb_conv2_fwd: null or aliased pointer");
   DRDB_SLOPE("drdb_conv2_fwd");
-  DRDB_SHAPE("drdb_conv2_fwd");
-  DRDB_TILES("drdb_conv2_fwd");
+  PAIF_SLAB_SHAPE("drdb_conv2_fwd", 1, "", 31);
+  PAIF_SLAB_TILES("drdb_conv2_fwd");
   const Plan pl = plan_of(12, false);
-  ConvArgs a;
-  a.in = in, a.mask = nullptr, a.out = c2, a.wpk = pack + ops_off(12, false), a.bias = pack + bias_off(12), a.bias2 = nullptr, a.slope = slope;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);
+  a.in = in, a.out = c2, a.wpk = pack + ops_off(12, false), a.bias = pack + bias_off(12), a.slope = slope;
   a.in_cs = CX, a.nq = CX / 4;
   a.out_cs = 32, a.out_off = 0, a.out_n = 32;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
-  launch_conv<9, false, EPI_ACT>(pl.MB, dim3((unsigned)(tx * ty * B), (unsigned)pl.groups), paif::as_stream(stream), a);
+  launch_conv<9, false, EPI_ACT>(pl.MB, conv_grid(pl, B, tx, ty), paif::as_stream(stream), a);
   PAIF_LAUNCH_CHECK("drdb_conv2_fwd");
   return 0;
 }
@@ -309,8 +253,9 @@ extern "C" int paif_drdb_conv2_fwd(const float* pack, float slope, const float* 
 extern "C" int paif_drdb_head_fwd(const float* pack, float slope, const float* c2, float* f, int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(pack && c2 && f, PAIF_EINVAL, "drdb_head_fwd: null pointer");
   DRDB_SLOPE("drdb_head_fwd");
-  DRDB_SHAPE("drdb_head_fwd");
-  hipLaunchKernelGGL(head_fwd_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, paif::as_stream(stream), pack, slope, c2, f, H, W, n);
+  PAIF_SLAB_SHAPE("drdb_head_fwd", 1, "", 31);
+  hipLaunchKernelGGL(head32_fwd_k<ACT_LEAKY>, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, paif::as_stream(stream), pack + PK_HEAD_W, slope, c2, f,
+                     H, W, n);
   PAIF_LAUNCH_CHECK("drdb_head_fwd");
   return 0;
 }
@@ -319,8 +264,9 @@ extern "C" int paif_drdb_head_bwd(const float* pack, float slope, const float* f
                                   paif_stream_t stream) {
   PAIF_REQUIRE(pack && f && d_f && d_c2, PAIF_EINVAL, "drdb_head_bwd: null pointer");
   DRDB_SLOPE("drdb_head_bwd");
-  DRDB_SHAPE("drdb_head_bwd");
-  hipLaunchKernelGGL(head_bwd_k, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, paif::as_stream(stream), pack, slope, f, d_f, d_c2, H, W, n);
+  PAIF_SLAB_SHAPE("drdb_head_bwd", 1, "", 31);
+  hipLaunchKernelGGL(head32_bwd_k<ACT_LEAKY>, dim3((unsigned)((n + 31) / 32)), dim3(256), 0, paif::as_stream(stream), pack + PK_HEAD_W, slope, f, d_f,
+                     d_c2, H, W, n);
   PAIF_LAUNCH_CHECK("drdb_head_bwd");
   return 0;
 }
@@ -330,15 +276,14 @@ extern "C" int paif_drdb_conv2_bwd(const float* pack, float slope, const float* 
   PAIF_REQUIRE(pack && c2 && d_c2 && d_in, PAIF_EINVAL, "drdb_conv2_bwd: null pointer");
   PAIF_REQUIRE(c2 != d_c2 && c2 != d_in && d_c2 != d_in, PAIF_EINVAL, "drdb_conv2_bwd: three different maps are expected");
   DRDB_SLOPE("drdb_conv2_bwd");
-  DRDB_SHAPE("drdb_conv2_bwd");
-  DRDB_TILES("drdb_conv2_bwd");
+  PAIF_SLAB_SHAPE("drdb_conv2_bwd", 1, "", 31);
+  PAIF_SLAB_TILES("drdb_conv2_bwd");
   const Plan pl = plan_of(12, true);
-  ConvArgs a;
-  a.in = d_c2, a.mask = c2, a.out = d_in, a.wpk = pack + ops_off(12, true), a.bias = nullptr, a.bias2 = nullptr, a.slope = slope;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);
+  a.in = d_c2, a.mask = c2, a.out = d_in, a.wpk = pack + ops_off(12, true), a.slope = slope;
   a.in_cs = 32, a.nq = 8;
   a.out_cs = CX, a.out_off = 0, a.out_n = CX;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
-  launch_conv<9, true, EPI_STORE>(pl.MB, dim3((unsigned)(tx * ty * B), (unsigned)pl.groups), paif::as_stream(stream), a);
+  launch_conv<9, true, EPI_STORE>(pl.MB, conv_grid(pl, B, tx, ty), paif::as_stream(stream), a);
   PAIF_LAUNCH_CHECK("drdb_conv2_bwd");
   return 0;
 }
@@ -350,19 +295,17 @@ extern "C" int paif_drdb_tail_bwd(const float* pack, int block, const float* r6,
   PAIF_REQUIRE(d_out_cs == SLAB || d_out_cs == CX, PAIF_EINVAL, "drdb_tail_bwd: d_out is [0, 64) of a 224-channel slab or a 64-channel map, not %d",
                d_out_cs);
   PAIF_REQUIRE(d_out != d_slab && r6 != d_slab && r6 != d_out, PAIF_EINVAL, "drdb_tail_bwd: three different maps are expected");
-  DRDB_SHAPE("drdb_tail_bwd");
-  DRDB_TILES("drdb_tail_bwd");
+  PAIF_SLAB_SHAPE("drdb_tail_bwd", 1, "", 31);
+  PAIF_SLAB_TILES("drdb_tail_bwd");
   const int l = 6 * block + 5;
   const Plan pl = plan_of(l, true);
   const hipStream_t s = paif::as_stream(stream);
-  ConvArgs a;
-  a.in = d_out, a.mask = r6, a.out = d_slab, a.wpk = pack + ops_off(l, true), a.bias = nullptr, a.bias2 = nullptr, a.slope = 0.f;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);   // slope 0: ReLU
+  a.in = d_out, a.mask = r6, a.out = d_slab, a.wpk = pack + ops_off(l, true);
   a.in_cs = d_out_cs, a.mask_cs = CX, a.in_scale = 1.f, a.nq = CX / 4;   // the mask has its own stride: the scaled staging, at scale 1
   a.out_cs = SLAB, a.out_off = 0, a.out_n = SLAB;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
   static_assert(plan_of(5, true).MB == 3 && plan_of(5, true).groups == 5, "224 output channels: five groups of three blocks, one block of padding");
-  hipLaunchKernelGGL((conv_k<1, 3, true, EPI_STORE, ACT_LEAKY, false, XIN_SCALED>), dim3((unsigned)(tx * ty * B), (unsigned)pl.groups), dim3(256), 0, s,
-                     a);
+  hipLaunchKernelGGL((conv_k<1, 3, true, EPI_STORE, ACT_LEAKY, false, XIN_SCALED>), conv_grid(pl, B, tx, ty), dim3(256), 0, s, a);
   PAIF_LAUNCH_CHECK("drdb_tail_bwd(conv)");
   hipLaunchKernelGGL(resid_add_k, dim3((unsigned)((n + 15) / 16)), dim3(256), 0, s, d_out, d_out_cs, d_slab, n);
   PAIF_LAUNCH_CHECK("drdb_tail_bwd(residual)");
@@ -373,18 +316,17 @@ extern "C" int paif_drdb_dcov_bwd(const float* pack, int block, int k, const flo
   PAIF_REQUIRE(pack && slab && d_slab && slab != d_slab, PAIF_EINVAL, "drdb_dcov_bwd: null or aliased pointer");
   DRDB_BLOCK("drdb_dcov_bwd");
   PAIF_REQUIRE(k >= 1 && k <= 5, PAIF_EINVAL, "drdb_dcov_bwd: Dcov%d does not exist", k);
-  DRDB_SHAPE("drdb_dcov_bwd");
-  DRDB_TILES("drdb_dcov_bwd");
+  PAIF_SLAB_SHAPE("drdb_dcov_bwd", 1, "", 31);
+  PAIF_SLAB_TILES("drdb_dcov_bwd");
   const int l = 6 * block + k - 1;
   const Layer y = layer_of(l);
   const Plan pl = plan_of(l, true);
-  ConvArgs a;
-  a.in = d_slab + y.cin, a.mask = slab + y.cin, a.out = d_slab, a.wpk = pack + ops_off(l, true), a.bias = nullptr, a.bias2 = nullptr, a.slope = 0.f;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);   // slope 0: ReLU
+  a.in = d_slab + y.cin, a.mask = slab + y.cin, a.out = d_slab, a.wpk = pack + ops_off(l, true);
   a.in_cs = SLAB, a.nq = GROW / 4;
   a.out_cs = SLAB, a.out_off = 0, a.out_n = y.cin;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
   PAIF_REQUIRE(pl.MB >= 3, PAIF_EINVAL, "drdb_dcov_bwd: unexpected plan");
-  launch_dil2<true, EPI_ADD>(pl.MB, dim3((unsigned)(tx * ty * B), (unsigned)pl.groups), paif::as_stream(stream), a);   // reads its own slice, adds below it
+  launch_dil2<true, EPI_ADD>(pl.MB, conv_grid(pl, B, tx, ty), paif::as_stream(stream), a);   // reads its own slice, adds below it
   PAIF_LAUNCH_CHECK("drdb_dcov_bwd");
   return 0;
 }
@@ -393,7 +335,7 @@ extern "C" int paif_drdb_stem_bwd(const float* pack, float slope, const float* s
                                   int W, paif_stream_t stream) {
   PAIF_REQUIRE(pack && slab && d_slab && d_ir && d_vis, PAIF_EINVAL, "drdb_stem_bwd: null pointer");
   DRDB_SLOPE("drdb_stem_bwd");
-  DRDB_SHAPE("drdb_stem_bwd");
+  PAIF_SLAB_SHAPE("drdb_stem_bwd", 1, "", 31);
   hipLaunchKernelGGL(stem_bwd_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, paif::as_stream(stream), pack, slope, slab, d_slab, d_ir, d_vis, H,
                      W, n);
   PAIF_LAUNCH_CHECK("drdb_stem_bwd");

@@ -257,10 +257,6 @@ __global__ __launch_bounds__(256) void head_bwd_k(const float* __restrict__ pack
   *reinterpret_cast<float4*>(ddec2 + i * 16 + 4 * cq) = s;
 }
 
-void pack_ops(const float* w, int co, int n, int off, const Plan& pl, int transposed, float* dst, hipStream_t s) {
-  hipLaunchKernelGGL(pack_ops_k, dim3((unsigned)((pl.floats() + 255) / 256)), dim3(256), 0, s, w, co, n, off, pl, transposed, dst);
-}
-
 }  // namespace
 
 extern "C" size_t paif_seafusion_pack_floats(void) { return PK_FLOATS; }
@@ -294,20 +290,11 @@ extern "C" int paif_seafusion_pack_conv(const float* w, const float* b, int conv
   return 0;
 }
 
-#define SEA_SHAPE(name)                                                                                   \
-  PAIF_REQUIRE(B >= 1 && H >= 1 && W >= 1, PAIF_EINVAL, name ": bad shape %d x %d x %d", B, H, W);          \
-  PAIF_REQUIRE((size_t)B* H* W < ((size_t)1 << 31), PAIF_EINVAL, name ": more than 2^31 pixels");           \
-  const size_t n = (size_t)B * H * W;                                                                       \
-  (void)n
-#define SEA_TILES(name)                                                                                   \
-  const int tx = (W + DT - 1) / DT, ty = (H + DT - 1) / DT;                                                 \
-  PAIF_REQUIRE((size_t)tx* ty* B < ((size_t)1 << 31), PAIF_EINVAL, name ": too many tiles")
-
 extern "C" int paif_seafusion_stem_fwd(const float* x, size_t sb, const float* pack, int stream_id, float* slab1, int B, int H, int W,
                                        paif_stream_t stream) {
   PAIF_REQUIRE(x && pack && slab1, PAIF_EINVAL, "seafusion_stem_fwd: null pointer");
   PAIF_REQUIRE(stream_id == 0 || stream_id == 1, PAIF_EINVAL, "seafusion_stem_fwd: stream %d is neither 0 (vis) nor 1 (inf)", stream_id);
-  SEA_SHAPE("seafusion_stem_fwd");
+  PAIF_SLAB_SHAPE("seafusion_stem_fwd", 1, "", 31);
   PAIF_REQUIRE((size_t)H * W <= sb, PAIF_EINVAL, "seafusion_stem_fwd: batch stride smaller than a plane");
   hipLaunchKernelGGL(stem_fwd_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, paif::as_stream(stream), x, sb, pack + PK_STEM + 160 * stream_id,
                      slab1, H, W, n);
@@ -319,17 +306,16 @@ extern "C" int paif_seafusion_conv_fwd(const float* pack, int layer, const float
   PAIF_REQUIRE(pack && in && out, PAIF_EINVAL, "seafusion_conv_fwd: null pointer");
   PAIF_REQUIRE(layer >= 0 && layer <= 10, PAIF_EINVAL, "seafusion_conv_fwd: layer %d outside [0, 10]", layer);
   PAIF_REQUIRE((layer < 8) == (in == out), PAIF_EINVAL, "seafusion_conv_fwd: a dense conv works inside its slab, a decoder conv from one map to another");
-  SEA_SHAPE("seafusion_conv_fwd");
-  SEA_TILES("seafusion_conv_fwd");
+  PAIF_SLAB_SHAPE("seafusion_conv_fwd", 1, "", 31);
+  PAIF_SLAB_TILES("seafusion_conv_fwd");
   const Layer y = layer_of(layer);
   const Plan pl = plan_of(layer, false);
   const int C = y.cout;
-  ConvArgs a;
-  a.in = in, a.mask = nullptr, a.out = out, a.wpk = pack + ops_off(layer, false), a.bias = pack + bias_off(layer), a.bias2 = nullptr, a.slope = SLOPE;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);
+  a.in = in, a.out = out, a.wpk = pack + ops_off(layer, false), a.bias = pack + bias_off(layer), a.slope = SLOPE;
   a.in_cs = layer < 8 ? 4 * C : y.cin, a.nq = y.cin / 4;
   a.out_cs = layer < 8 ? 4 * C : y.cout, a.out_off = layer < 8 ? C * (1 + (layer & 1)) : 0, a.out_n = y.cout;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
-  launch_conv<9, false, EPI_ACT>(pl.MB, dim3((unsigned)(tx * ty * B), (unsigned)pl.groups), paif::as_stream(stream), a);
+  launch_conv<9, false, EPI_ACT>(pl.MB, conv_grid(pl, B, tx, ty), paif::as_stream(stream), a);
   PAIF_LAUNCH_CHECK("seafusion_conv_fwd");
   return 0;
 }
@@ -337,7 +323,7 @@ extern "C" int paif_seafusion_conv_fwd(const float* pack, int layer, const float
 extern "C" int paif_seafusion_sobel_fwd(const float* pack, int block, float* slab, void* sgn, int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(pack && slab && sgn, PAIF_EINVAL, "seafusion_sobel_fwd: null pointer");
   PAIF_REQUIRE(block >= 0 && block <= 3, PAIF_EINVAL, "seafusion_sobel_fwd: block %d outside [0, 3]", block);
-  SEA_SHAPE("seafusion_sobel_fwd");
+  PAIF_SLAB_SHAPE("seafusion_sobel_fwd", 1, "", 31);
   const int C = blk_c(block);
   const size_t work = n * (C / 4);
   hipLaunchKernelGGL(sobel_fwd_k, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, paif::as_stream(stream), pack + dw_off(block), slab,
@@ -350,24 +336,23 @@ extern "C" int paif_seafusion_tail_fwd(const float* pack, int block, const float
   PAIF_REQUIRE(pack && slab && out, PAIF_EINVAL, "seafusion_tail_fwd: null pointer");
   PAIF_REQUIRE(block >= 0 && block <= 3, PAIF_EINVAL, "seafusion_tail_fwd: block %d outside [0, 3]", block);
   PAIF_REQUIRE(slab != out, PAIF_EINVAL, "seafusion_tail_fwd: the output map must not be the block's own slab");
-  SEA_SHAPE("seafusion_tail_fwd");
-  SEA_TILES("seafusion_tail_fwd");
+  PAIF_SLAB_SHAPE("seafusion_tail_fwd", 1, "", 31);
+  PAIF_SLAB_TILES("seafusion_tail_fwd");
   const Plan pl = tail_plan(block, false);
   const int C = blk_c(block), r = block & 1;
-  ConvArgs a;
-  a.in = slab, a.mask = nullptr, a.out = out, a.wpk = pack + tail_ops_off(block, false);
+  ConvArgs a = conv_args(pl, H, W, tx, ty);
+  a.in = slab, a.out = out, a.wpk = pack + tail_ops_off(block, false);
   a.bias = pack + tail_bias_off(block, 0), a.bias2 = pack + tail_bias_off(block, 1), a.slope = SLOPE_RGBD;
   a.in_cs = 4 * C, a.nq = C;
   a.out_cs = r ? ENC : 128, a.out_off = r ? 48 * (block >> 1) : 0, a.out_n = blk_cout(block);
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
-  launch_conv<1, false, EPI_ACT>(pl.MB, dim3((unsigned)(tx * ty * B), (unsigned)pl.groups), paif::as_stream(stream), a);
+  launch_conv<1, false, EPI_ACT>(pl.MB, conv_grid(pl, B, tx, ty), paif::as_stream(stream), a);
   PAIF_LAUNCH_CHECK("seafusion_tail_fwd");
   return 0;
 }
 
 extern "C" int paif_seafusion_head_fwd(const float* pack, const float* dec2, float* fused, int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(pack && dec2 && fused, PAIF_EINVAL, "seafusion_head_fwd: null pointer");
-  SEA_SHAPE("seafusion_head_fwd");
+  PAIF_SLAB_SHAPE("seafusion_head_fwd", 1, "", 31);
   hipLaunchKernelGGL(head_fwd_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, paif::as_stream(stream), pack, dec2, fused, H, W, n);
   PAIF_LAUNCH_CHECK("seafusion_head_fwd");
   return 0;
@@ -376,7 +361,7 @@ extern "C" int paif_seafusion_head_fwd(const float* pack, const float* dec2, flo
 extern "C" int paif_seafusion_head_bwd(const float* pack, const float* fused, const float* d_fused, float* d_dec2, int B, int H, int W,
                                        paif_stream_t stream) {
   PAIF_REQUIRE(pack && fused && d_fused && d_dec2, PAIF_EINVAL, "seafusion_head_bwd: null pointer");
-  SEA_SHAPE("seafusion_head_bwd");
+  PAIF_SLAB_SHAPE("seafusion_head_bwd", 1, "", 31);
   hipLaunchKernelGGL(head_bwd_k, dim3((unsigned)((n + 63) / 64)), dim3(256), 0, paif::as_stream(stream), pack, fused, d_fused, d_dec2, H, W, n);
   PAIF_LAUNCH_CHECK("seafusion_head_bwd");
   return 0;
@@ -388,17 +373,16 @@ extern "C" int paif_seafusion_conv_bwd(const float* pack, int layer, const float
   PAIF_REQUIRE(layer >= 0 && layer <= 10, PAIF_EINVAL, "seafusion_conv_bwd: layer %d outside [0, 10]", layer);
   PAIF_REQUIRE(taped != d_out && taped != d_in, PAIF_EINVAL, "seafusion_conv_bwd: the gradient maps must not alias the taped maps");
   PAIF_REQUIRE((layer < 8) == (d_out == d_in), PAIF_EINVAL, "seafusion_conv_bwd: a dense conv works inside d_slab, a decoder conv from one map to another");
-  SEA_SHAPE("seafusion_conv_bwd");
-  SEA_TILES("seafusion_conv_bwd");
+  PAIF_SLAB_SHAPE("seafusion_conv_bwd", 1, "", 31);
+  PAIF_SLAB_TILES("seafusion_conv_bwd");
   const Layer y = layer_of(layer);
   const Plan pl = plan_of(layer, true);
   const int C = y.cout, off = layer < 8 ? C * (1 + (layer & 1)) : 0, cs = layer < 8 ? 4 * C : y.cout;   // where the layer's output lives
-  ConvArgs a;
-  a.in = d_out + off, a.mask = taped + off, a.out = d_in, a.wpk = pack + ops_off(layer, true), a.bias = nullptr, a.bias2 = nullptr, a.slope = SLOPE;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);
+  a.in = d_out + off, a.mask = taped + off, a.out = d_in, a.wpk = pack + ops_off(layer, true), a.slope = SLOPE;
   a.in_cs = cs, a.nq = y.cout / 4;
   a.out_cs = layer < 8 ? 4 * C : y.cin, a.out_off = 0, a.out_n = y.cin;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
-  const dim3 grid((unsigned)(tx * ty * B), (unsigned)pl.groups);
+  const dim3 grid = conv_grid(pl, B, tx, ty);
   if (layer < 8) launch_conv<9, true, EPI_ADD>(pl.MB, grid, paif::as_stream(stream), a);   // reads its own slice of d_slab, adds below it
   else launch_conv<9, true, EPI_STORE>(pl.MB, grid, paif::as_stream(stream), a);
   PAIF_LAUNCH_CHECK("seafusion_conv_bwd");
@@ -410,17 +394,15 @@ extern "C" int paif_seafusion_tail_bwd(const float* pack, int block, const float
   PAIF_REQUIRE(pack && taped_out && d_out && d_slab, PAIF_EINVAL, "seafusion_tail_bwd: null pointer");
   PAIF_REQUIRE(block >= 0 && block <= 3, PAIF_EINVAL, "seafusion_tail_bwd: block %d outside [0, 3]", block);
   PAIF_REQUIRE(d_out != d_slab && taped_out != d_slab && taped_out != d_out, PAIF_EINVAL, "seafusion_tail_bwd: three different maps are expected");
-  SEA_SHAPE("seafusion_tail_bwd");
-  SEA_TILES("seafusion_tail_bwd");
+  PAIF_SLAB_SHAPE("seafusion_tail_bwd", 1, "", 31);
+  PAIF_SLAB_TILES("seafusion_tail_bwd");
   const Plan pl = tail_plan(block, true);
   const int C = blk_c(block), r = block & 1, off = r ? 48 * (block >> 1) : 0;
-  ConvArgs a;
-  a.in = d_out + off, a.mask = taped_out + off, a.out = d_slab, a.wpk = pack + tail_ops_off(block, true), a.bias = nullptr, a.bias2 = nullptr;
-  a.slope = SLOPE_RGBD;
+  ConvArgs a = conv_args(pl, H, W, tx, ty);
+  a.in = d_out + off, a.mask = taped_out + off, a.out = d_slab, a.wpk = pack + tail_ops_off(block, true), a.slope = SLOPE_RGBD;
   a.in_cs = r ? ENC : 128, a.nq = blk_cout(block) / 4;
   a.out_cs = 4 * C, a.out_off = 0, a.out_n = 4 * C;
-  a.chunks = pl.chunks, a.H = H, a.W = W, a.tx = tx, a.ty = ty;
-  launch_conv<1, true, EPI_STORE>(pl.MB, dim3((unsigned)(tx * ty * B), (unsigned)pl.groups), paif::as_stream(stream), a);
+  launch_conv<1, true, EPI_STORE>(pl.MB, conv_grid(pl, B, tx, ty), paif::as_stream(stream), a);
   PAIF_LAUNCH_CHECK("seafusion_tail_bwd");
   return 0;
 }
@@ -428,7 +410,7 @@ extern "C" int paif_seafusion_tail_bwd(const float* pack, int block, const float
 extern "C" int paif_seafusion_sobel_bwd(const float* pack, int block, const void* sgn, float* d_slab, int B, int H, int W, paif_stream_t stream) {
   PAIF_REQUIRE(pack && sgn && d_slab, PAIF_EINVAL, "seafusion_sobel_bwd: null pointer");
   PAIF_REQUIRE(block >= 0 && block <= 3, PAIF_EINVAL, "seafusion_sobel_bwd: block %d outside [0, 3]", block);
-  SEA_SHAPE("seafusion_sobel_bwd");
+  PAIF_SLAB_SHAPE("seafusion_sobel_bwd", 1, "", 31);
   const int C = blk_c(block);
   const size_t work = n * (C / 4);
   hipLaunchKernelGGL(sobel_bwd_k, dim3((unsigned)((work + 255) / 256)), dim3(256), 0, paif::as_stream(stream), pack + dw_off(block),
@@ -441,7 +423,7 @@ extern "C" int paif_seafusion_stem_bwd(const float* pack, int stream_id, const f
                                        paif_stream_t stream) {
   PAIF_REQUIRE(pack && slab1 && d_slab1 && d_x, PAIF_EINVAL, "seafusion_stem_bwd: null pointer");
   PAIF_REQUIRE(stream_id == 0 || stream_id == 1, PAIF_EINVAL, "seafusion_stem_bwd: stream %d is neither 0 (vis) nor 1 (inf)", stream_id);
-  SEA_SHAPE("seafusion_stem_bwd");
+  PAIF_SLAB_SHAPE("seafusion_stem_bwd", 1, "", 31);
   hipLaunchKernelGGL(stem_bwd_k, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, paif::as_stream(stream), pack + PK_STEM + 160 * stream_id, slab1,
                      d_slab1, d_x, H, W, n);
   PAIF_LAUNCH_CHECK("seafusion_stem_bwd");

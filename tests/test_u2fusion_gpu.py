@@ -226,6 +226,38 @@ def test_settings_that_do_not_apply_change_nothing(golden):
         ops.CONFIG["two_stream"] = old["two_stream"]
 
 
+@pytest.mark.parametrize("shape", ((1, 13, 17), (2, 9, 20)))
+@pytest.mark.parametrize("layer", (7, 8))
+def test_sub_convs_equal_the_generic_slab_conv_bit_for_bit(golden, layer, shape):
+    """sub.1 (128 -> 64, four blocks per workgroup) and sub.2 (64 -> 32, two) are the two layers whose channel counts the generic entry
+    point onto csrc/conv_slab.h (paif_bffusion_conv) accepts: paif_u2fusion_conv_fwd / _bwd and that entry point run one kernel on one
+    operand order, so the same weights give the same bits, forward and transposed.  The generic transpose has the add form only: it
+    adds onto a zeroed map.  1x13x17: two tiles across, ragged both ways; 2x9x20: two images."""
+    B, H, W = shape
+    L, dev = ops.lib(), _dev()
+    sd = _sd(golden)
+    convs = [(sd[n + ".weight"].to(dev), sd[n + ".bias"].to(dev)) for n, _, _ in S.U2FUSION_CONVS]
+    pack = ops.u2fusion_pack(convs)
+    w, b = convs[layer]
+    cout, cin = w.shape[:2]
+    cv = ops._BffConv([(w, 0)], cout, cin, 9, b, 0.2, 0)
+    x = t(S.make_feature(310 + layer, (B, H, W, cin))).to(dev)
+    taped = t(S.make_feature(320 + layer, (B, H, W, cout))).to(dev)
+    d_out = t(S.make_feature(330 + layer, (B, H, W, cout))).to(dev)
+    assert float(taped.min()) < 0 < float(taped.max()) and float(x.min()) < 0 < float(x.max())
+    mine, other = torch.empty_like(taped), torch.empty_like(taped)
+    ops._lib.check(L.paif_u2fusion_conv_fwd(ops._p(pack), layer, ops._p(x), ops._p(mine), B, H, W, ops._stream()), "u2fusion_conv_fwd")
+    ops._bff_conv(cv, x, 0, other, 0, B, H, W)
+    assert float(mine.min()) < 0 < float(mine.max())
+    assert torch.equal(mine, other)
+    d_mine, d_other = torch.empty_like(x), torch.zeros_like(x)
+    ops._lib.check(L.paif_u2fusion_conv_bwd(ops._p(pack), layer, ops._p(taped), ops._p(d_out), ops._p(d_mine), B, H, W, ops._stream()),
+                   "u2fusion_conv_bwd")
+    ops._bff_conv_t(cv, taped, d_out, 0, d_other, 0, None, True, 0, B, H, W)
+    assert float(d_mine.abs().max()) > 0
+    assert torch.equal(d_mine, d_other)
+
+
 def test_wrong_planes_are_refused_on_the_device(golden):
     net = _net(golden)
     z = torch.zeros(1, 1, 8, 8, device=_dev())
