@@ -14,23 +14,20 @@ state_dict (8 modules) but the reference never applies it, so it loads and has n
 in .train() mode raises: batch-statistics BatchNorm is not built.  The used BatchNorms' four tensors and the LayerNorm affine are part of
 the pack's key (an in-place change rebuilds the pack); the BatchNorm and LayerNorm eps floats are compared per call.
 
-It implements the protocol of the fusion network inside the composite models (forward_impl / backward_impl with a tape), so
-`Network_MM_CompModel(BFFR(), ...)` runs through `attack_both` and the robustness harness.  The composite calls the reference's
-forward(image_vis_y, image_ir) positionally as forward(ir[:, 0:1], Y[:, 0:1]): the infrared plane runs through conv1_vi / DB*_vi (and
-attn2), Y through conv1_ir / DB*_ir (and attn1).
+The composite calls the reference's forward(image_vis_y, image_ir) positionally as forward(ir[:, 0:1], Y[:, 0:1]): the infrared plane
+runs through conv1_vi / DB*_vi (and attn2), Y through conv1_ir / DB*_ir (and attn1).
 
-Built: fp32 planes with H, W >= 16 (the level-4 map is (H // 8) x (W // 8) and takes reflection padding by 1).  Not built (raises):
-parameter gradients, .train() mode.  The maps stay fp32 under ops.set_storage("bf16" | "f16"), and the conv_precision / gemm_precision
-settings and ops.CONFIG["two_stream"] do not apply: there is one arithmetic (exact fp32).  Sobelxy, DenseBlock_light, conv1x1 and
-qkv_transform are carried as the reference carries them: names without a use."""
+The composite protocol, what is not built and the settings that do not apply: fusion_model/_native.py.  Built: fp32 planes with
+H, W >= 16 (the level-4 map is (H // 8) x (W // 8) and takes reflection padding by 1).  Not built either: .train() mode.  Sobelxy,
+DenseBlock_light, conv1x1 and qkv_transform are carried as the reference carries them: names without a use."""
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..operations_m import _PackCache, grad_anchor
+from ..operations_m import _PackCache
+from ._native import NativeFusion
 
-_NO_WGRAD = "BFFusion: parameter gradients (training the baseline) are not built"
 _NO_TRAIN = ("BFFusion: training-mode BatchNorm (batch statistics) is not built -- call .eval(), as every reference flow does; the running "
              "statistics are not used in its place")
 MIN_SIZE = 16
@@ -155,8 +152,9 @@ class FusionBlock_res(nn.Module):
         self.attn2 = SelfAttention(channels, num_heads)
 
 
-class BFFR(nn.Module):
+class BFFR(NativeFusion):
     """fusion_model/BFFusion.py, class BFFR."""
+    NAME = "BFFusion"
 
     def __init__(self, device=None):
         super().__init__()
@@ -233,15 +231,9 @@ class BFFR(nn.Module):
             self._packs, self._pack_eps = _PackCache(), eps
         return self._packs.get("bffusion", key, lambda: ops.bffusion_pack(spec))
 
-    @staticmethod
-    def _check_planes(x0, x1):
-        for t in (x0, x1):
-            if not t.is_cuda:
-                raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor -- there is no CPU path" % t.device)
-            if t.dtype != torch.float32:
-                raise TypeError("BFFusion: fp32 planes are expected, got %s" % t.dtype)
-        if x0.dim() != 4 or x0.shape[1] != 1 or x0.shape != x1.shape:
-            raise ValueError("BFFusion: two [B,1,H,W] planes of one shape are expected, got %s and %s" % (tuple(x0.shape), tuple(x1.shape)))
+    @classmethod
+    def _check_planes(cls, x0, x1):
+        super()._check_planes(x0, x1)
         if x0.shape[2] < MIN_SIZE or x0.shape[3] < MIN_SIZE:
             raise ValueError("BFFusion: H, W >= 16 are needed (the level-4 map is (H // 8) x (W // 8) and takes reflection padding by 1), "
                              "got [B,1,H,W] = %s" % (tuple(x0.shape),))
@@ -253,15 +245,7 @@ class BFFR(nn.Module):
     # ---- the reference's interface --------------------------------------------------------------------------------------
     def forward(self, image_vis_y, image_ir):
         """-> the fused plane [B,1,H,W] in (0, 1).  image_vis_y runs through the `_vi` modules, image_ir through the `_ir` modules."""
-        self._check_mode()
-        if ops.want_param_grads(self):
-            raise NotImplementedError(_NO_WGRAD + " -- freeze the parameters (requires_grad_(False)), or run under ops.no_param_grads() / "
-                                      "torch.no_grad() for input gradients")
-        self._check_planes(image_vis_y, image_ir)
-        if torch.is_grad_enabled() and (image_vis_y.requires_grad or image_ir.requires_grad):
-            return _BFFRFn.apply(image_vis_y, image_ir, self, grad_anchor(image_vis_y.device))
-        with torch.no_grad():
-            return self._run(image_vis_y, image_ir, None)
+        return self._gate(image_vis_y, image_ir)
 
     def _run(self, x0, x1, tape):
         maps, fused = ops.bffusion_forward(x0, x1, self._pack())
@@ -286,47 +270,6 @@ class BFFR(nn.Module):
         out += [maps["D"][lvl][..., off:off + m] for (lvl, _, _, _, _, off, m) in ops.BFF_DEC]
         return out + [maps["A"][l][s]["ctx"][:, None] for l in range(4) for s in range(2)]
 
-    def _features(self, image_vis_y, image_ir):
-        """The taped maps (_map_list) as NCHW tensors -- for the tests."""
-        self._check_mode()
-        self._check_planes(image_vis_y, image_ir)
-        with torch.no_grad():
-            maps, _ = ops.bffusion_forward(image_vis_y, image_ir, self._pack())
-        return [m.permute(0, 3, 1, 2).contiguous() for m in self._map_list(maps)]
-
-    # ---- the composite models' protocol (core/model_fusion_auto.py: _CompositeBase) -------------------------
-    def forward_impl(self, ir, vis, inter=None, tape=None):
-        """ir, vis: [B,>=1,H,W], channel 0 is used.  The composite calls the reference's forward(ir[:, 0:1], Y[:, 0:1]) positionally: the
-        infrared plane enters image_vis_y (the `_vi` modules), Y enters image_ir -> fused [B,1,H,W]; tape (dict): filled for
-        backward_impl."""
-        if inter is not None:
-            raise NotImplementedError("BFFusion: `inter` (the searched network's decomposition intermediates) does not apply")
-        if tape is not None and ops.taping_wgrad():
-            raise NotImplementedError(_NO_WGRAD)
-        self._check_mode()
-        x0, x1 = ir[:, 0:1, :, :], vis[:, 0:1, :, :]
-        self._check_planes(x0, x1)
-        return self._run(x0, x1, tape)
-
-    def backward_impl(self, d_fused, tape, wgrad=False):
-        """d/d(fused) [B,1,H,W] -> (d/d(image_vis_y), d/d(image_ir)) as [B,1,H,W] each: inside the composite, (d/d(ir), d/d(Y))."""
-        if wgrad:
-            raise NotImplementedError(_NO_WGRAD + " (wgrad=True)")
+    def _reverse(self, d_fused, tape):
+        """d/d(fused) -> (d/d(image_vis_y), d/d(image_ir)): inside the composite, (d/d(ir), d/d(Y))."""
         return ops.bffusion_backward(tape["maps"], tape["out"], d_fused, self._pack())
-
-
-class _BFFRFn(torch.autograd.Function):
-    """Autograd node of BFFR: hand-written reverse pass, input gradients only."""
-
-    @staticmethod
-    def forward(ctx, x0, x1, module, anchor):
-        tape = {}
-        out = module._run(x0.detach(), x1.detach(), tape)
-        ctx.tape, ctx.module = tape, module
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        d0, d1 = ctx.module.backward_impl(d_out.contiguous(), ctx.tape)
-        ctx.tape = None
-        return d0, d1, None, None

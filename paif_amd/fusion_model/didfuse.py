@@ -9,20 +9,16 @@ The running statistics and the PReLU slopes are part of the pack's key: an in-pl
 slopes are read to the host when the pack is built (never inside a hipGraph capture) and must be >= 0: the reverse pass reads the PReLU
 branch off the taped output.
 
-It implements the protocol of the fusion network inside the composite models (forward_impl / backward_impl with a tape), so
-`Network_MM_CompModel(DID(), ...)` runs through `attack_both` and the robustness harness like the searched network.  The composite calls
-forward(ir[:, 0:1], Y[:, 0:1]): the infrared plane enters x_over / AE_Encoder1.
+The composite calls forward(ir[:, 0:1], Y[:, 0:1]): the infrared plane enters x_over / AE_Encoder1, Y enters x_under / AE_Encoder2.
 
-Built: fp32 planes with H, W >= 2 (reflection padding).  Not built (raises): parameter gradients (training the baseline), .train() mode.
-The maps stay fp32 under ops.set_storage("bf16" | "f16"), and the conv_precision / gemm_precision settings and ops.CONFIG["two_stream"] do
-not apply: there is one arithmetic (exact fp32)."""
-import torch
+The composite protocol, what is not built and the settings that do not apply: fusion_model/_native.py.  Built: fp32 planes with
+H, W >= 2 (reflection padding).  Not built either: .train() mode."""
 import torch.nn as nn
 
 from .. import ops
-from ..operations_m import _PackCache, grad_anchor
+from ..operations_m import _PackCache
+from ._native import NativeFusion
 
-_NO_WGRAD = "DIDFuse: parameter gradients (training the baseline) are not built"
 _NO_TRAIN = ("DIDFuse: training-mode BatchNorm (batch statistics) is not built -- call .eval(), as every reference flow does; the running "
              "statistics are not used in its place")
 
@@ -107,8 +103,9 @@ class AE_Decoder(nn.Module):
         self.cov7 = Cov7()
 
 
-class DID(nn.Module):
+class DID(NativeFusion):
     """fusion_model/AUIF.py:131-150."""
+    NAME = "DIDFuse"
 
     def __init__(self):
         super().__init__()
@@ -149,16 +146,9 @@ class DID(nn.Module):
             self._packs, self._pack_eps = _PackCache(), eps
         return self._packs.get("didfuse", params, lambda: ops.didfuse_pack(convs, slopes))
 
-    @staticmethod
-    def _check_planes(x_over, x_under):
-        for t in (x_over, x_under):
-            if not t.is_cuda:
-                raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor -- there is no CPU path" % t.device)
-            if t.dtype != torch.float32:
-                raise TypeError("DIDFuse: fp32 planes are expected, got %s" % t.dtype)
-        if x_over.dim() != 4 or x_over.shape[1] != 1 or x_over.shape != x_under.shape:
-            raise ValueError("DIDFuse: two [B,1,H,W] planes of one shape are expected, got %s and %s"
-                             % (tuple(x_over.shape), tuple(x_under.shape)))
+    @classmethod
+    def _check_planes(cls, x_over, x_under):
+        super()._check_planes(x_over, x_under)
         if x_over.shape[2] < 2 or x_over.shape[3] < 2:
             raise ValueError("DIDFuse: reflection padding by 1 needs H, W >= 2 (as torch's ReflectionPad2d), got [B,1,H,W] = %s"
                              % (tuple(x_over.shape),))
@@ -170,15 +160,7 @@ class DID(nn.Module):
     # ---- the reference's interface --------------------------------------------------------------------------------------
     def forward(self, x_over, x_under):
         """fusion_model/AUIF.py:141-150 -> the fused plane [B,1,H,W] in (0, 1)."""
-        self._check_mode()
-        if ops.want_param_grads(self):
-            raise NotImplementedError(_NO_WGRAD + " -- freeze the parameters (requires_grad_(False)), or run under ops.no_param_grads() / "
-                                      "torch.no_grad() for input gradients")
-        self._check_planes(x_over, x_under)
-        if torch.is_grad_enabled() and (x_over.requires_grad or x_under.requires_grad):
-            return _DIDFn.apply(x_over, x_under, self, grad_anchor(x_over.device))
-        with torch.no_grad():
-            return self._run(x_over, x_under, None)
+        return self._gate(x_over, x_under)
 
     def _run(self, x_over, x_under, tape):
         maps, fused = ops.didfuse_forward(x_over, x_under, self._pack())
@@ -196,47 +178,6 @@ class DID(nn.Module):
         out += [maps["d2"][..., 64:128], maps["d1"][..., 64:128], maps["bd"][..., 0:64], maps["bd"][..., 64:128]]
         return out + [maps["d1"][..., 0:64], maps["d2"][..., 0:64]]
 
-    def _features(self, x_over, x_under):
-        """The 14 taped maps (_map_list) as NCHW tensors -- for the tests."""
-        self._check_mode()
-        self._check_planes(x_over, x_under)
-        with torch.no_grad():
-            maps, _ = ops.didfuse_forward(x_over, x_under, self._pack())
-        return [m.permute(0, 3, 1, 2).contiguous() for m in self._map_list(maps)]
-
-    # ---- the composite models' protocol (core/model_fusion_auto.py: _CompositeBase) -------------------------
-    def forward_impl(self, ir, vis, inter=None, tape=None):
-        """ir, vis: [B,>=1,H,W], channel 0 is used.  The composite calls the reference's forward(ir[:, 0:1], Y[:, 0:1]) positionally: the
-        infrared plane enters x_over (AE_Encoder1), Y enters x_under (AE_Encoder2) -> fused [B,1,H,W]; tape (dict): filled for
-        backward_impl."""
-        if inter is not None:
-            raise NotImplementedError("DIDFuse: `inter` (the searched network's decomposition intermediates) does not apply")
-        if tape is not None and ops.taping_wgrad():
-            raise NotImplementedError(_NO_WGRAD)
-        self._check_mode()
-        x_over, x_under = ir[:, 0:1, :, :], vis[:, 0:1, :, :]
-        self._check_planes(x_over, x_under)
-        return self._run(x_over, x_under, tape)
-
-    def backward_impl(self, d_fused, tape, wgrad=False):
-        """d/d(fused) [B,1,H,W] -> (d/d(x_over), d/d(x_under)) as [B,1,H,W] each: inside the composite, (d/d(ir), d/d(Y))."""
-        if wgrad:
-            raise NotImplementedError(_NO_WGRAD + " (wgrad=True)")
+    def _reverse(self, d_fused, tape):
+        """d/d(fused) -> (d/d(x_over), d/d(x_under)): inside the composite, (d/d(ir), d/d(Y))."""
         return ops.didfuse_backward(tape["maps"], tape["out"], d_fused, self._pack())
-
-
-class _DIDFn(torch.autograd.Function):
-    """Autograd node of DID: hand-written reverse pass, input gradients only."""
-
-    @staticmethod
-    def forward(ctx, x_over, x_under, module, anchor):
-        tape = {}
-        out = module._run(x_over.detach(), x_under.detach(), tape)
-        ctx.tape, ctx.module = tape, module
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        d1, d2 = ctx.module.backward_impl(d_out.contiguous(), ctx.tape)
-        ctx.tape = None
-        return d1, d2, None, None

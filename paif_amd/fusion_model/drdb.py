@@ -11,20 +11,16 @@ this code.  The reverse pass follows torch: the gradient of an extremum is sprea
 reaches f only where the clamp passes (0 <= f <= 1).  That even split comes with the plane kernels; the fixtures hold no exact tie among
 unclamped pixels, so it is not covered by the tests of this network.
 
-It implements the protocol of the fusion network inside the composite models (forward_impl / backward_impl with a tape), so
-`Network_MM_CompModel(Fusion_Network(), ...)` runs through `attack_both` and the robustness harness like the searched network.
-
-Built: fp32 planes of any size; DRDB alone at in_ch = 64, growth_rate = 32.  Not built (raises): parameter gradients (training).  The
-maps stay fp32 under ops.set_storage("bf16" | "f16"), and the conv_precision / gemm_precision settings and ops.CONFIG["two_stream"] do
-not apply: there is one arithmetic (exact fp32).  The PReLU slope is read on the host when the weights are packed (never inside a graph
+The composite protocol, what is not built and the settings that do not apply: fusion_model/_native.py.  Built: fp32 planes of any size;
+DRDB alone at in_ch = 64, growth_rate = 32.  The PReLU slope is read on the host when the weights are packed (never inside a graph
 capture) and must be >= 0: the reverse pass reads the branch off the taped output."""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..operations_m import _PackCache, grad_anchor
+from ._native import NativeFusion, need_device
 
-_NO_WGRAD = "Fusion_Network: parameter gradients (training the network) are not built"
 _NO_WGRAD_DRDB = "DRDB: parameter gradients (training the block) are not built"
 _FREEZE = (" -- freeze the parameters (requires_grad_(False)), or run under ops.no_param_grads() / torch.no_grad() for input gradients")
 
@@ -54,8 +50,7 @@ class DRDB(nn.Module):
     def _check(self, x):
         if self._shape != (64, 32):
             raise NotImplementedError("DRDB: only in_ch = 64, growth_rate = 32 (the form Fusion_Network uses) is built, got %s" % (self._shape,))
-        if not x.is_cuda:
-            raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor -- there is no CPU path" % x.device)
+        need_device(x)
         if x.dtype != torch.float32:
             raise TypeError("DRDB: an fp32 map is expected, got %s" % x.dtype)
         if x.dim() != 4 or x.shape[1] != 64:
@@ -87,8 +82,11 @@ class _DRDBFn(torch.autograd.Function):
         return d_x, None, None
 
 
-class Fusion_Network(nn.Module):
+class Fusion_Network(NativeFusion):
     """core/model_fusion_auto.py:159-188."""
+    NAME = "Fusion_Network"
+    TRAINING = "training the network"
+    SHAPE_NOTE = " (channel 0 of ir and of vis)"
 
     def __init__(self):
         super().__init__()
@@ -111,17 +109,6 @@ class Fusion_Network(nn.Module):
         return self._packs.get("drdb", params, lambda: ops.drdb_pack(convs, self.relu.weight))
 
     @staticmethod
-    def _check_planes(ir, vis):
-        for t in (ir, vis):
-            if not t.is_cuda:
-                raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor -- there is no CPU path" % t.device)
-            if t.dtype != torch.float32:
-                raise TypeError("Fusion_Network: fp32 planes are expected, got %s" % t.dtype)
-        if ir.dim() != 4 or ir.shape[1] != 1 or ir.shape != vis.shape:
-            raise ValueError("Fusion_Network: two [B,1,H,W] planes of one shape are expected (channel 0 of ir and of vis), got %s and %s"
-                             % (tuple(ir.shape), tuple(vis.shape)))
-
-    @staticmethod
     def _first_channel(x):
         """x[:, 0:1] of the reference: any channel count >= 1."""
         if x.dim() == 4 and x.shape[1] > 1:
@@ -131,14 +118,7 @@ class Fusion_Network(nn.Module):
     # ---- the reference's interface --------------------------------------------------------------------------------------
     def forward(self, ir, vis):
         """core/model_fusion_auto.py:170-188 -> the fused plane [B,1,H,W] in [0, 1], normalised over the batch."""
-        if ops.want_param_grads(self):
-            raise NotImplementedError(_NO_WGRAD + _FREEZE)
-        ir, vis = self._first_channel(ir), self._first_channel(vis)
-        self._check_planes(ir, vis)
-        if torch.is_grad_enabled() and (ir.requires_grad or vis.requires_grad):
-            return _FusionNetworkFn.apply(ir, vis, self, grad_anchor(ir.device))
-        with torch.no_grad():
-            return self._run(ir, vis, None)
+        return self._gate(self._first_channel(ir), self._first_channel(vis))
 
     def _run(self, ir, vis, tape):
         maps, fused = ops.drdb_forward(ir, vis, self._pack())
@@ -157,44 +137,8 @@ class Fusion_Network(nn.Module):
         return out + [maps["c2"], maps["f"].permute(0, 2, 3, 1)]
 
     def _features(self, ir, vis):
-        """The 17 taped maps (_map_list) as NCHW tensors -- for the tests."""
-        ir, vis = self._first_channel(ir), self._first_channel(vis)
-        self._check_planes(ir, vis)
-        with torch.no_grad():
-            maps, _ = ops.drdb_forward(ir, vis, self._pack())
-        return [m.permute(0, 3, 1, 2).contiguous() for m in self._map_list(maps)]
+        return super()._features(self._first_channel(ir), self._first_channel(vis))
 
-    # ---- the composite models' protocol (core/model_fusion_auto.py: _CompositeBase) -------------------------
-    def forward_impl(self, ir, vis, inter=None, tape=None):
-        """ir, vis: [B,>=1,H,W], channel 0 is used (inside the composite: the infrared plane and Y) -> fused [B,1,H,W]; tape (dict):
-        filled for backward_impl."""
-        if inter is not None:
-            raise NotImplementedError("Fusion_Network: `inter` (the searched network's decomposition intermediates) does not apply")
-        if tape is not None and ops.taping_wgrad():
-            raise NotImplementedError(_NO_WGRAD)
-        ir, vis = ir[:, 0:1, :, :], vis[:, 0:1, :, :]
-        self._check_planes(ir, vis)
-        return self._run(ir, vis, tape)
-
-    def backward_impl(self, d_fused, tape, wgrad=False):
-        """d/d(fused) [B,1,H,W] -> (d/d(ir), d/d(vis)) as [B,1,H,W] each."""
-        if wgrad:
-            raise NotImplementedError(_NO_WGRAD + " (wgrad=True)")
+    def _reverse(self, d_fused, tape):
+        """d/d(fused) -> (d/d(ir), d/d(vis))."""
         return ops.drdb_backward(tape["maps"], d_fused, self._pack())
-
-
-class _FusionNetworkFn(torch.autograd.Function):
-    """Autograd node of Fusion_Network: hand-written reverse pass, input gradients only."""
-
-    @staticmethod
-    def forward(ctx, ir, vis, module, anchor):
-        tape = {}
-        out = module._run(ir.detach(), vis.detach(), tape)
-        ctx.tape, ctx.module = tape, module
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        d1, d2 = ctx.module.backward_impl(d_out.contiguous(), ctx.tape)
-        ctx.tape = None
-        return d1, d2, None, None

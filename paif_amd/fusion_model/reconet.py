@@ -2,17 +2,17 @@
 state_dict keys (a checkpoint of the reference class loads with strict=True); forward and the reverse pass (input gradients) launch the
 kernels of csrc/reconet.hip, one launch per recurrence, the 3*dim-channel map never in memory.
 
-It implements the protocol of the fusion network inside the composite models (forward_impl / backward_impl with a tape), so
-`Network_MM_CompModel(ReCoNet(3, 64, False), ...)` runs through `attack_both` and the robustness harness like the searched network.
+The composite protocol and what is not built: fusion_model/_native.py; `forward_impl` takes `init_f` as well.
 
-Built: depth >= 1, dim 16 / 32 / 64, BatchNorm in eval mode (folded into the packed weights), fp32 planes of any size.  Not built (raises):
-parameter gradients (training the baseline), train-mode BatchNorm.  The planes stay fp32 under ops.set_storage("bf16" | "f16") -- they have
-one channel, there is no traffic to save -- and ops.CONFIG["two_stream"] does not apply."""
+Built: depth >= 1, dim 16 / 32 / 64, BatchNorm in eval mode (folded into the packed weights), fp32 planes of any size.  Not built either:
+train-mode BatchNorm.  The planes stay fp32 under ops.set_storage("bf16" | "f16") because they have one channel: there is no traffic to
+save."""
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..operations_m import _PackCache, grad_anchor
+from ..operations_m import _PackCache
+from ._native import NativeFusion
 
 DIMS = (16, 32, 64)
 
@@ -42,8 +42,9 @@ class DGroup(nn.Module):
         raise NotImplementedError("DGroup holds parameters only: the arithmetic runs inside ReCoNet's fused kernels")
 
 
-class ReCoNet(nn.Module):
+class ReCoNet(NativeFusion):
     """fusion_model/Reconet.py:55-105."""
+    NAME = "ReCoNet"
 
     def __init__(self, depth: int, dim: int, use_bn: bool):
         super().__init__()
@@ -78,34 +79,22 @@ class ReCoNet(nn.Module):
         return self._packs.get("reconet", params, lambda: ops.reconet_pack(self.att_a_conv.weight, self.att_b_conv.weight, groups,
                                                                            cs.weight, cs.bias, self.dim))
 
-    @staticmethod
-    def _check_planes(i_1, i_2):
-        for t in (i_1, i_2):
-            if not t.is_cuda:
-                raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor -- there is no CPU path" % t.device)
-            if t.dtype != torch.float32:
-                raise TypeError("ReCoNet: fp32 planes are expected, got %s" % t.dtype)
-        if i_1.dim() != 4 or i_1.shape[1] != 1 or i_1.shape != i_2.shape:
-            raise ValueError("ReCoNet: two [B,1,H,W] planes of one shape are expected, got %s and %s" % (tuple(i_1.shape), tuple(i_2.shape)))
+    @classmethod
+    def _no_wgrad_true(cls):
+        return "ReCoNet: parameter gradients (wgrad=True, training the baseline) are not built"
 
     # ---- the reference's interface --------------------------------------------------------------------------------------
     def forward(self, i_1, i_2, init_f: str = 'max', show_detail: bool = False):
         """fusion_model/Reconet.py:67-80: -> the last i_f, or (list of depth+1 i_f, list of att_a, list of att_b) under show_detail."""
-        if ops.want_param_grads(self):
-            raise NotImplementedError("ReCoNet: parameter gradients (training the baseline) are not built -- freeze the parameters "
-                                      "(requires_grad_(False)), or run under ops.no_param_grads() / torch.no_grad() for input gradients")
-        self._check_planes(i_1, i_2)
-        if torch.is_grad_enabled() and (i_1.requires_grad or i_2.requires_grad):
-            if show_detail:
-                raise NotImplementedError("ReCoNet: show_detail returns the intermediate planes without an autograd node -- call it "
-                                          "under torch.no_grad()")
-            return _ReCoNetFn.apply(i_1, i_2, self, init_f, grad_anchor(i_1.device))
+        if not show_detail:
+            return self._gate(i_1, i_2, init_f)
+        if self._wants_node(i_1, i_2):
+            raise NotImplementedError("ReCoNet: show_detail returns the intermediate planes without an autograd node -- call it "
+                                      "under torch.no_grad()")
         with torch.no_grad():
-            if show_detail:
-                tape = {}
-                self._run(i_1, i_2, init_f, tape)
-                return tape["i_f"], tape["att_a"], tape["att_b"]
-            return self._run(i_1, i_2, init_f, None)
+            tape = {}
+            self._run(i_1, i_2, init_f, tape)
+            return tape["i_f"], tape["att_a"], tape["att_b"]
 
     def _run(self, i_1, i_2, init_f, tape):
         pack = self._pack()
@@ -126,19 +115,12 @@ class ReCoNet(nn.Module):
     def forward_impl(self, ir, vis, inter=None, tape=None, init_f='max'):
         """ir, vis: [B,>=1,H,W], channel 0 is used (i_1 = infrared, i_2 = visible Y) -> fused [B,1,H,W]; tape (dict): filled for
         backward_impl (the depth+1 i_f planes and the attention maps: 3*depth+1 planes, nothing wide)."""
-        if inter is not None:
-            raise NotImplementedError("ReCoNet: `inter` (the searched network's decomposition intermediates) does not apply")
-        if tape is not None and ops.taping_wgrad():
-            raise NotImplementedError("ReCoNet: parameter gradients (training the baseline) are not built")
-        i_1, i_2 = ir[:, 0:1, :, :], vis[:, 0:1, :, :]
-        self._check_planes(i_1, i_2)
+        i_1, i_2 = self._impl_planes(ir, vis, inter, tape)
         return self._run(i_1, i_2, init_f, tape)
 
-    def backward_impl(self, d_fused, tape, wgrad=False):
+    def _reverse(self, d_fused, tape):
         """d/d(fused) [B,1,H,W] -> (d/d(i_1), d/d(i_2)) as [B,1,H,W] each.  Ties: see csrc/reconet.hip (the channel max of the attention
         input routes a tie to the image plane, the initialisation's elementwise max splits it)."""
-        if wgrad:
-            raise NotImplementedError("ReCoNet: parameter gradients (wgrad=True, training the baseline) are not built")
         pack = self._pack()
         i_1, i_2, fs = tape["i_1"], tape["i_2"], tape["i_f"]
         d_f = d_fused.contiguous()
@@ -149,20 +131,3 @@ class ReCoNet(nn.Module):
                                        accumulate=k != self.depth - 1)
         ops.reconet_init_bwd_(d_i1, d_i2, i_1, i_2, tape["use_max"], d_f)
         return d_i1, d_i2
-
-
-class _ReCoNetFn(torch.autograd.Function):
-    """Autograd node of ReCoNet: hand-written reverse pass, input gradients only."""
-
-    @staticmethod
-    def forward(ctx, i_1, i_2, module, init_f, anchor):
-        tape = {}
-        out = module._run(i_1.detach(), i_2.detach(), init_f, tape)
-        ctx.tape, ctx.module = tape, module
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        d_i1, d_i2 = ctx.module.backward_impl(d_out.contiguous(), ctx.tape)
-        ctx.tape = None
-        return d_i1, d_i2, None, None, None

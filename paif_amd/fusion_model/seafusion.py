@@ -7,20 +7,14 @@ Three things of the reference are kept as they are: the decoder's BatchNorm modu
 and .train() alike; the Sobel filters are parameters -- initialised to the stencil, read from the weight pack like any other weight; and
 inside the composite models the INFRARED plane enters `image_vis` (Network_MM_CompModel calls forward(ir[:, 0:1], Y[:, 0:1])).
 
-It implements the protocol of the fusion network inside the composite models (forward_impl / backward_impl with a tape), so
-`Network_MM_CompModel(SeaFusion(), ...)` runs through `attack_both` and the robustness harness like the searched network.
-
-Built: fp32 planes of any size.  Not built (raises): parameter gradients (training the baseline).  The maps stay fp32 under
-ops.set_storage("bf16" | "f16"), and the conv_precision / gemm_precision settings and ops.CONFIG["two_stream"] do not apply: there is one
-arithmetic (exact fp32)."""
+The composite protocol, what is not built and the settings that do not apply: fusion_model/_native.py.  Built: fp32 planes of any size."""
 import numpy as np
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..operations_m import _PackCache, grad_anchor
-
-_NO_WGRAD = "SeaFusion: parameter gradients (training the baseline) are not built"
+from ..operations_m import _PackCache
+from ._native import NativeFusion
 
 
 # ---- the reference's member classes, as parameter containers: SeaFusion's kernels do the arithmetic ---------------------------------
@@ -96,8 +90,10 @@ class RGBD(nn.Module):
         self.convup = Conv1(in_channels, out_channels)
 
 
-class SeaFusion(nn.Module):
+class SeaFusion(NativeFusion):
     """fusion_model/SeaFusion.py:86-125."""
+    NAME = "SeaFusion"
+    SHAPE_NOTE = " (image_vis[:, :1] and a one-channel image_ir)"
 
     def __init__(self):
         super().__init__()
@@ -132,17 +128,6 @@ class SeaFusion(nn.Module):
         return self._packs.get("seafusion", params, lambda: ops.seafusion_pack(convs))
 
     @staticmethod
-    def _check_planes(x_vis, x_inf):
-        for t in (x_vis, x_inf):
-            if not t.is_cuda:
-                raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor -- there is no CPU path" % t.device)
-            if t.dtype != torch.float32:
-                raise TypeError("SeaFusion: fp32 planes are expected, got %s" % t.dtype)
-        if x_vis.dim() != 4 or x_vis.shape[1] != 1 or x_vis.shape != x_inf.shape:
-            raise ValueError("SeaFusion: two [B,1,H,W] planes of one shape are expected (image_vis[:, :1] and a one-channel image_ir), "
-                             "got %s and %s" % (tuple(x_vis.shape), tuple(x_inf.shape)))
-
-    @staticmethod
     def _first_channel(image_vis):
         """image_vis[:, :1] of the reference: any channel count >= 1."""
         if image_vis.dim() == 4 and image_vis.shape[1] > 1:
@@ -152,15 +137,7 @@ class SeaFusion(nn.Module):
     # ---- the reference's interface --------------------------------------------------------------------------------------
     def forward(self, image_vis, image_ir):
         """fusion_model/SeaFusion.py:105-125 -> the fused plane [B,1,H,W] in (0, 1)."""
-        if ops.want_param_grads(self):
-            raise NotImplementedError(_NO_WGRAD + " -- freeze the parameters (requires_grad_(False)), or run under ops.no_param_grads() / "
-                                      "torch.no_grad() for input gradients")
-        x_vis = self._first_channel(image_vis)
-        self._check_planes(x_vis, image_ir)
-        if torch.is_grad_enabled() and (x_vis.requires_grad or image_ir.requires_grad):
-            return _SeaFusionFn.apply(x_vis, image_ir, self, grad_anchor(x_vis.device))
-        with torch.no_grad():
-            return self._run(x_vis, image_ir, None)
+        return self._gate(self._first_channel(image_vis), image_ir)
 
     def _run(self, x_vis, x_inf, tape):
         maps, fused = ops.seafusion_forward(x_vis, x_inf, self._pack())
@@ -181,45 +158,9 @@ class SeaFusion(nn.Module):
         return out + [maps["dec4"], maps["dec3"], maps["dec2"]]
 
     def _features(self, image_vis, image_ir):
-        """The 21 taped maps (_map_list) as NCHW tensors -- for the tests."""
-        x_vis = self._first_channel(image_vis)
-        self._check_planes(x_vis, image_ir)
-        with torch.no_grad():
-            maps, _ = ops.seafusion_forward(x_vis, image_ir, self._pack())
-        return [m.permute(0, 3, 1, 2).contiguous() for m in self._map_list(maps)]
+        return super()._features(self._first_channel(image_vis), image_ir)
 
-    # ---- the composite models' protocol (core/model_fusion_auto.py: _CompositeBase) -------------------------
-    def forward_impl(self, ir, vis, inter=None, tape=None):
-        """ir, vis: [B,>=1,H,W], channel 0 is used.  The composite calls the reference's forward(ir[:, 0:1], Y[:, 0:1]) positionally: the
-        infrared plane enters image_vis (the vis_* stream), Y enters image_ir (the inf_* stream) -> fused [B,1,H,W]; tape (dict): filled
-        for backward_impl."""
-        if inter is not None:
-            raise NotImplementedError("SeaFusion: `inter` (the searched network's decomposition intermediates) does not apply")
-        if tape is not None and ops.taping_wgrad():
-            raise NotImplementedError(_NO_WGRAD)
-        image_vis, image_ir = ir[:, 0:1, :, :], vis[:, 0:1, :, :]
-        self._check_planes(image_vis, image_ir)
-        return self._run(image_vis, image_ir, tape)
-
-    def backward_impl(self, d_fused, tape, wgrad=False):
-        """d/d(fused) [B,1,H,W] -> (d/d(image_vis), d/d(image_ir)) as [B,1,H,W] each: inside the composite, (d/d(ir), d/d(Y))."""
-        if wgrad:
-            raise NotImplementedError(_NO_WGRAD + " (wgrad=True)")
+    def _reverse(self, d_fused, tape):
+        """d/d(fused) -> (d/d(image_vis), d/d(image_ir)): inside the composite, where the infrared plane enters image_vis (the vis_*
+        stream) and Y enters image_ir (the inf_* stream), (d/d(ir), d/d(Y))."""
         return ops.seafusion_backward(tape["maps"], tape["out"], d_fused, self._pack())
-
-
-class _SeaFusionFn(torch.autograd.Function):
-    """Autograd node of SeaFusion: hand-written reverse pass, input gradients only."""
-
-    @staticmethod
-    def forward(ctx, x_vis, x_inf, module, anchor):
-        tape = {}
-        out = module._run(x_vis.detach(), x_inf.detach(), tape)
-        ctx.tape, ctx.module = tape, module
-        return out
-
-    @staticmethod
-    def backward(ctx, d_out):
-        d1, d2 = ctx.module.backward_impl(d_out.contiguous(), ctx.tape)
-        ctx.tape = None
-        return d1, d2, None, None

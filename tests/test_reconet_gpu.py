@@ -8,21 +8,17 @@ import numpy as np
 import pytest
 import torch
 
-from paif_amd import ops, synthetic as S
-from tests import helpers as Hh
-from tests.helpers import t, maxabs
+from tests import baseline_common as C
+from tests.baseline_common import border, dev, exact_arithmetic  # noqa: F401  (exact_arithmetic is a fixture)
+from tests.helpers import t
 
 pytestmark = pytest.mark.gpu
 
 CONFIGS = {"d3c16": (3, 16, False), "d2c16bn": (2, 16, True), "d3c64": (3, 64, False)}
 CASES = ("2x48x64", "1x37x53", "1x4x5")
 INITS = ("max", "mean")
+HALO = 5            # the total halo of one recurrence
 EPS, ALPHA = 8 / 255., 2 / 255.
-
-
-def _dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _net(golden, key):
@@ -32,23 +28,16 @@ def _net(golden, key):
     pre = "sd_%s/" % key
     net = ReCoNet(*CONFIGS[key]).eval()
     net.load_state_dict({k[len(pre):]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith(pre)}, strict=True)
-    return net.requires_grad_(False).to(_dev())
+    return net.requires_grad_(False).to(dev())
 
 
 def _inputs(golden, case):
     g = golden("gr_reconet")
-    return t(g["i1_" + case]).to(_dev()), t(g["i2_" + case]).to(_dev()), t(g["cot_" + case]).to(_dev())
+    return t(g["i1_" + case]).to(dev()), t(g["i2_" + case]).to(dev()), t(g["cot_" + case]).to(dev())
 
 
 def _bound(ref32, ref64):
     return 1.5 * float(np.abs(ref32.astype(np.float64) - ref64).max()) + 1e-5
-
-
-def _border(a):
-    """The outermost 5 rows / columns (the total halo of one recurrence) of [..., H, W]."""
-    m = np.ones(a.shape[-2:], dtype=bool)
-    m[5:-5, 5:-5] = False
-    return a[..., m]
 
 
 @pytest.mark.parametrize("init", INITS)
@@ -75,7 +64,7 @@ def test_forward_matches_the_reference(golden, key, case, init):
             print("%s %s %s %s[%d]: err %.3e bound %.3e" % (key, case, init, name, k, err, bound))
             assert err <= bound, (name, k, err, bound)
             if case == "2x48x64":
-                eb = float(np.abs(_border(got) - _border(ref64)).max())
+                eb = float(np.abs(border(got, HALO) - border(ref64, HALO)).max())
                 assert eb <= bound, (name, k, "border", eb, bound)
 
 
@@ -104,199 +93,51 @@ def test_input_gradients_match_float64_autograd(golden, key, case, init):
 
 
 def test_reverse_pass_is_linear_in_the_cotangent(golden):
-    """backward_impl(g1) + backward_impl(g2) = backward_impl(g1 + g2) to fp32 rounding.  Bound: every output is a sum of a few thousand fp32
-    products with cancellation, so the three results differ by accumulated rounding, relative to the largest gradient well below 1e-4; a
-    dropped or doubled term shows at order 1."""
-    net = _net(golden, "d3c64")
-    i1, i2, cot = _inputs(golden, "1x37x53")
-    tape = {}
-    with torch.no_grad():
-        net.forward_impl(i1, i2, tape=tape)
-        g2 = t(S.make_feature(77, tuple(cot.shape))).to(_dev())
-        r1, r2, r12 = net.backward_impl(cot, tape), net.backward_impl(g2, tape), net.backward_impl(ops.add(cot, g2), tape)
-    for x, y, z in zip(r1, r2, r12):
-        scale = max(1.0, float(z.abs().max()))
-        err = float((x + y - z).abs().max())
-        print("linearity: err %.3e scale %.3e" % (err, scale))
-        assert err <= 1e-4 * scale
+    """backward_impl(g1) + backward_impl(g2) = backward_impl(g1 + g2) to fp32 rounding: within 1e-4 of the largest gradient
+    (tests/baseline_common.py says why)."""
+    C.reverse_pass_is_linear_in_the_cotangent(_net(golden, "d3c64"), *_inputs(golden, "1x37x53"), rtol=1e-4)
 
 
 def test_two_runs_are_bit_identical(golden):
-    net = _net(golden, "d3c16")
-    i1, i2, cot = _inputs(golden, "2x48x64")
-    runs = []
-    with torch.no_grad():
-        for _ in range(2):
-            tape = {}
-            f = net.forward_impl(i1, i2, tape=tape)
-            runs.append((f,) + tuple(net.backward_impl(cot, tape)))
-    for x, y in zip(*runs):
-        assert torch.equal(x, y)
+    C.two_runs_are_bit_identical(_net(golden, "d3c16"), *_inputs(golden, "2x48x64"), taped=lambda tape: [])
 
 
 def test_channel_slices_are_taken_without_a_copy(golden):
     """The composite hands over ir[:, 0:1] and ycc[:, 0:1] of multi-channel tensors: planes addressed through their batch stride."""
-    net = _net(golden, "d3c16")
-    i1, i2, cot = _inputs(golden, "2x48x64")
-    wide1 = torch.cat([i1, i1 * 0.5, i1 * 0.25], 1).contiguous()
-    wide2 = torch.cat([i2, i2 * 0.5], 1).contiguous()
-    with torch.no_grad():
-        ta, tb = {}, {}
-        fa = net.forward_impl(i1, i2, tape=ta)
-        fb = net.forward_impl(wide1, wide2, tape=tb)
-        assert torch.equal(fa, fb)
-        for x, y in zip(net.backward_impl(cot, ta), net.backward_impl(cot, tb)):
-            assert torch.equal(x, y)
+    C.channel_slices_are_taken_without_a_copy(_net(golden, "d3c16"), *_inputs(golden, "2x48x64"))
 
 
 # ---- inside the composite model ------------------------------------------------------------------------------------------------
-@pytest.fixture
-def exact_arithmetic():
-    """The setting tests/test_attack_gpu.py asserts gradient parity under: exact-fp32 conv and GEMM kernels."""
-    old, oldg = ops.CONFIG["conv_precision"], ops.CONFIG["gemm_precision"]
-    ops.set_conv_precision("f32")
-    ops.set_gemm_precision("f32")
-    yield
-    ops.set_conv_precision(old)
-    ops.set_gemm_precision(oldg)
-
-
-def _composite(golden):
-    """As tests/test_attack_gpu.py:_model, with the baseline as the fusion module; its weights are the fixture's."""
-    from paif_amd.core.model_fusion_auto import Network_MM_CompModel
+def _in_composite(golden):
+    """The network with the fixture's weights as the fusion module of Network_MM_CompModel."""
     from paif_amd.fusion_model.reconet import ReCoNet
 
     g = golden("gr_reconet_attack")
-    m = Network_MM_CompModel(ReCoNet(3, 16, False), None, None, "mit_b0", num_classes=9).eval()
-    S.load_formula_weights(m, head=Hh.HEAD64["mit_b0"])
-    m.enhance_net.load_state_dict({k[3:]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith("sd/")}, strict=True)
-    return m.to(_dev())
-
-
-def _batch(start=0):
-    ir, vis, lab = S.make_batch(2, 64, 96, start=start)
-    return t(ir).to(_dev()), t(vis).to(_dev()), t(lab).to(_dev())
-
-
-def _scale(a):
-    return max(1.0, float(np.abs(a).max()))
+    return C.composite(ReCoNet(3, 16, False), {k[3:]: torch.from_numpy(np.asarray(v)) for k, v in g.items() if k.startswith("sd/")})
 
 
 def test_composite_clean_forward(golden):
-    """Tolerances of tests/test_seg_gpu.py::test_full_model_config1_4x64x96: fused 1e-4, logits 2e-4 x scale, argmax agreement 99.9 %."""
+    """fused within 1e-4, logits within 2e-4 x scale, argmax agreement 99.9 %: the tolerances of
+    tests/test_seg_gpu.py::test_full_model_config1_4x64x96."""
     g = golden("gr_reconet_attack")
-    m = _composite(golden)
-    ir, vis, lab = _batch()
-    with torch.no_grad():
-        fused, seg = m(ir, vis)
-    print("composite: fused err %.3e logits err %.3e" % (maxabs(fused.cpu(), g["fused"]), maxabs(seg.cpu(), g["logits"])))
-    assert maxabs(fused.cpu(), g["fused"]) <= 1e-4
-    assert maxabs(seg.cpu(), g["logits"]) <= 2e-4 * _scale(g["logits"])
-    up = torch.nn.functional.interpolate(seg.cpu(), size=lab.shape[1:], mode="bilinear", align_corners=False)
-    assert (up.argmax(1).numpy() == g["pred"]).mean() >= 0.999
-
-
-def _check_attack(g, d_ir, d_vis, trace, loss_rtol, frac):
-    """tests/test_attack_gpu.py:_check_attack."""
-    losses = np.array([s["loss"] for s in trace])
-    np.testing.assert_allclose(losses, g["losses"], rtol=loss_rtol)
-    for mine, ref in ((trace[-1]["g_ir"], g["gsum_ir"]), (trace[-1]["g_vis"], g["gsum_vis"])):
-        assert (np.sign(mine.cpu().numpy()) != np.sign(ref)).mean() <= frac
-    for mine, ref in ((d_ir, g["delta_ir"]), (d_vis, g["delta_vis"])):
-        a = mine.detach().cpu().numpy()
-        assert (np.abs(a - ref) > 1e-6).mean() <= frac
-        assert np.abs(a).max() <= 8 / 255. + 1e-7
+    C.composite_clean_forward(_in_composite(golden), g, start=0, fused_atol=1e-4, logits_rtol=2e-4, agreement=0.999)
 
 
 def test_attack_both_pgd_through_the_baseline(golden, exact_arithmetic):
-    from paif_amd.attack.attack import attack_both
-
+    """Losses rtol 1e-4, sign and delta mismatch <= 2e-3, against the reference's float32 trace."""
     g = golden("gr_reconet_attack")
-    m = _composite(golden)
-    assert hasattr(m, "forward_taped")                       # the fast path of attack.py is the one taken
-    ir, vis, lab = _batch()
-    trace = []
-    with torch.no_grad():
-        d_ir, d_vis = attack_both(m, vis, ir, lab, epsilon=EPS, alpha=ALPHA, attack_iters=3, attack_loss='l_seg', attack_way='PGD',
-                                  delta0_ir=t(g["d0_ir"]), delta0_vis=t(g["d0_vis"]), trace=trace)
-    for s in trace:
-        assert s["g_ir"].grad_fn is None and s["g_vis"].grad_fn is None and not s["g_ir"].requires_grad
-    print("attack: losses %s reference %s" % ([s["loss"] for s in trace], list(g["losses"])))
-    _check_attack(g, d_ir, d_vis, trace, 1e-4, 2e-3)
-
-
-def _pgd_iterations(m, ir, vis, lab64, d_ir, d_vis, g_ir, g_vis, gs, iters):
-    """The fast path of attack.py:_attack_loop, in place on d_*, g_* (so that it can be captured)."""
-    for i in range(iters):
-        with ops.attack_forward_arithmetic():
-            _, logits, tape = m.forward_taped(ops.add(ir, d_ir), ops.add(vis, d_vis))
-        way, wt, wf = ops.attack_loss_weights('PGD', i, iters)
-        coef = ops.attack_loss_fwd(logits, lab64, way, wt, wf)
-        d32 = ops.attack_loss_bwd(logits, lab64, coef, way, wt, wf, upstream=gs)
-        with ops.attack_backward_arithmetic():
-            gi, gv = m.backward_taped(d32, tape)
-        ops.axpy_(g_ir, gi.contiguous(), 1.0 / gs)
-        ops.pgd_step_(d_ir, g_ir, ir, ALPHA, EPS)
-        ops.axpy_(g_vis, gv.contiguous(), 1.0 / gs)
-        ops.pgd_step_(d_vis, g_vis, vis, ALPHA, EPS)
+    C.attack_both_pgd(_in_composite(golden), g, start=0, eps=EPS, alpha=ALPHA, loss_rtol=1e-4, frac=2e-3)
 
 
 def test_pgd_iterations_replayed_from_a_graph_are_bit_identical(golden):
-    """Three PGD iterations captured once with torch.cuda.graph and replayed = the eager loop.  Single stream, no parallel branches."""
+    """Three PGD iterations captured once with torch.cuda.graph and replayed = the eager loop (tests/baseline_common.py: one
+    eager pass first, one side stream, no parallel branches)."""
     g = golden("gr_reconet_attack")
-    m = _composite(golden)
-    ir, vis, lab = _batch()
-    lab64 = lab.type(torch.long).contiguous()
-    d0_ir, d0_vis = t(g["d0_ir"]).to(_dev()), t(g["d0_vis"]).to(_dev())
-    state = [torch.zeros_like(x) for x in (ir, vis, ir, vis)]
-
-    def reset():
-        state[0].copy_(d0_ir), state[1].copy_(d0_vis), state[2].zero_(), state[3].zero_()
-
-    gstream = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), ops.attack_arithmetic():
-        gs = ops.attack_grad_scale(lab64)
-        reset()
-        _pgd_iterations(m, ir, vis, lab64, *state, gs, 3)     # eager: also builds every weight pack outside the capture
-        eager = [x.clone() for x in state]
-        torch.cuda.synchronize()
-        with torch.cuda.stream(gstream):
-            reset()
-            _pgd_iterations(m, ir, vis, lab64, *state, gs, 3)
-            torch.cuda.synchronize()
-            with torch.cuda.graph(graph, stream=gstream):
-                _pgd_iterations(m, ir, vis, lab64, *state, gs, 3)
-        torch.cuda.synchronize()
-        reset()
-        torch.cuda.synchronize()
-        graph.replay()
-        torch.cuda.synchronize()
-    assert float(eager[2].abs().max()) > 0
-    for x, y in zip(eager, state):
-        assert torch.equal(x, y)
+    C.pgd_iterations_replayed_from_a_graph_are_bit_identical(_in_composite(golden), start=0,
+                                                             delta0=lambda ir, vis: (t(g["d0_ir"]), t(g["d0_vis"])), eps=EPS, alpha=ALPHA)
 
 
 def test_robustness_harnesses_run_with_the_baseline(golden):
     """val_segformer_robust2 (clean) and val_segformer_robust (PGD, 2 iterations) on two 2x64x96 batches: finite mIoU, and the clean one is
     what the confusion matrix of the model's own seg_map argmax gives."""
-    from oracle import paif_oracle as O
-    from paif_amd.harness import val_segformer_robust, val_segformer_robust2
-
-    m = _composite(golden)
-    batches = []
-    for start in (0, 2):
-        ir, vis, lab = _batch(start)
-        batches.append((vis, ir, lab))
-    clean = val_segformer_robust2(m, batches)
-    conf = np.zeros((9, 9), dtype=np.int64)
-    with torch.no_grad():
-        for vis, ir, lab in batches:
-            _, seg = m(ir, vis)
-            up = torch.nn.functional.interpolate(seg.cpu(), size=lab.shape[1:], mode="bilinear", align_corners=False)
-            conf += O.confusion_matrix(lab.cpu().numpy(), up.argmax(1).numpy())
-    iou = O.compute_results(conf)[2]
-    assert np.isfinite(clean["miou"])
-    assert abs(clean["miou"] - float(np.mean(np.nan_to_num(iou)))) <= 1e-12
-    rob = val_segformer_robust(m, batches, attack_iters=2)
-    assert np.isfinite(rob["miou"])
+    C.robustness_harnesses_run(_in_composite(golden), miou_atol=1e-12, attack_iters=2)

@@ -2,7 +2,7 @@
 outputs and autograd (tests/golden/gs_seafusion*.npz, generated on the CPU by tools/make_golden_seafusion.py), and inside the composite
 model / attack / harness flow of the searched network.
 
-Bound of the kernel parity checks (tests/test_u2fusion_gpu.py): with floor = max|ref32 - ref64| of the same tensor,
+Bound of the kernel parity checks (tests/baseline_common.py: bound): with floor = max|ref32 - ref64| of the same tensor,
 max|hip - ref64| <= 1.5 * floor + 1e-5 * max(1, max|ref64|).  One kernel form exists (exact fp32, the 3x3 and 1x1 convs on
 v_mfma_f32_16x16x4_f32); it is the default build.
 
@@ -19,8 +19,9 @@ import torch
 import torch.nn.functional as F
 
 from paif_amd import ops, synthetic as S
-from tests import helpers as Hh
-from tests.helpers import t, maxabs
+from tests import baseline_common as C
+from tests.baseline_common import check, dev, exact_arithmetic, floor  # noqa: F401  (exact_arithmetic is a fixture)
+from tests.helpers import t
 
 pytestmark = pytest.mark.gpu
 
@@ -28,13 +29,9 @@ GRAD_CASES = ("1x4x5", "1x13x17", "2x9x20", "1x5x37", "1x19x18")
 LARGE = ("1x37x53", "2x24x32")
 SMALL = ("1x4x5", "1x13x17")
 MAP_CHANNELS = [16, 16, 16, 16, 32, 32, 32, 32, 48] * 2 + [64, 32, 16]
+HALO = 10           # the ten 3 x 3 convs on the longest path
 EPS, ALPHA = 8 / 255., 2 / 255.
 _SD = {}
-
-
-def _dev():
-    assert torch.cuda.is_available()
-    return torch.device("cuda:0")
 
 
 def _sd(golden):
@@ -50,43 +47,13 @@ def _net(golden):
 
     net = SeaFusion().eval()
     net.load_state_dict(_sd(golden), strict=True)
-    return net.requires_grad_(False).to(_dev())
+    return net.requires_grad_(False).to(dev())
 
 
 def _inputs(golden, case):
     g = golden("gs_seafusion_" + case)
     cot = g["cot"] if "cot" in g else S.make_feature(900 + len(case), g["i1"].shape)
-    return t(g["i1"]).to(_dev()), t(g["i2"]).to(_dev()), t(cot).to(_dev())
-
-
-def _bound(floor, ref64):
-    return 1.5 * floor + 1e-5 * max(1.0, float(np.abs(ref64).max()))
-
-
-def _floor(ref32, ref64):
-    return float(np.abs(ref32.astype(np.float64) - ref64).max())
-
-
-def _border(a):
-    """The outermost 10 rows / columns (the total halo of the ten 3 x 3 convs on the longest path) of [..., H, W]."""
-    m = np.ones(a.shape[-2:], dtype=bool)
-    m[10:-10, 10:-10] = False
-    return a[..., m]
-
-
-def _check(what, case, name, mine, ref64, floor, border=False, keep=None):
-    got = mine.detach().cpu().numpy().astype(np.float64)
-    assert got.shape == ref64.shape
-    if keep is not None:                       # excluded elements take no part: neither in the error nor in the border check
-        got = np.where(keep, got, ref64)
-    bound = _bound(floor, ref64)
-    err = float(np.abs(got - ref64).max())
-    print("%s %s %s: err %.3e bound %.3e ratio %.3f scale %.3e" % (what, case, name, err, bound, err / bound, float(np.abs(ref64).max())))
-    assert err <= bound, (name, err, bound)
-    if border:
-        eb = float(np.abs(_border(got) - _border(ref64)).max())
-        print("%s %s %s border: err %.3e bound %.3e ratio %.3f" % (what, case, name, eb, bound, eb / bound))
-        assert eb <= bound, (name, "border", eb, bound)
+    return t(g["i1"]).to(dev()), t(g["i2"]).to(dev()), t(cot).to(dev())
 
 
 @pytest.mark.parametrize("case", GRAD_CASES + LARGE)
@@ -100,7 +67,7 @@ def test_fused_plane_matches_the_reference(golden, case):
     with torch.no_grad():
         out = net(i1, i2)
     assert out.grad_fn is None and out.shape == i1.shape
-    _check("fused", case, "fused", out, g["fused64"], _floor(g["fused"], g["fused64"]), border=case in LARGE)
+    check("fused", case, "fused", out, g["fused64"], floor(g["fused"], g["fused64"]), halo=HALO if case in LARGE else None)
 
 
 @pytest.mark.parametrize("case", SMALL)
@@ -114,7 +81,7 @@ def test_feature_maps_match_the_reference(golden, case):
     assert [m.shape[1] for m in maps] == MAP_CHANNELS and sum(MAP_CHANNELS) == 592
     for k, m in enumerate(maps):
         g = parts[0 if k < 9 else 1]
-        _check("maps", case, "map%d" % k, m, g["map%d" % k], float(g["map_floor"][k]))
+        check("maps", case, "map%d" % k, m, g["map%d" % k], float(g["map_floor"][k]))
 
 
 @pytest.mark.parametrize("case", GRAD_CASES)
@@ -128,7 +95,7 @@ def test_input_gradients_match_float64_autograd(golden, case):
     assert out.grad_fn is not None
     (out * cot).sum().backward()
     for name, mine in (("d_i1", a.grad), ("d_i2", b.grad)):
-        _check("grad", case, name, mine, g[name + "64"], _floor(g[name], g[name + "64"]))
+        check("grad", case, name, mine, g[name + "64"], floor(g[name], g[name + "64"]))
 
 
 def _nchw(m):
@@ -215,7 +182,7 @@ def test_reverse_pass_matches_its_float64_restatement_on_the_taped_branches(gold
     r64 = _linearised(_sd(golden), br, dtanh, i1.cpu(), i2.cpu(), cot.cpu(), torch.float64)
     r32 = _linearised(_sd(golden), br, dtanh, i1.cpu(), i2.cpu(), cot.cpu(), torch.float32)
     for name, mine, a64, a32 in (("d_i1", d1, r64[0], r32[0]), ("d_i2", d2, r64[1], r32[1])):
-        _check("taped-mask reverse", case, name, mine, a64, _floor(a32, a64), border=True, keep=keep)
+        check("taped-mask reverse", case, name, mine, a64, floor(a32, a64), halo=HALO, keep=keep)
 
 
 def _flat(tape):
@@ -224,84 +191,38 @@ def _flat(tape):
 
 
 def test_reverse_pass_is_linear_in_the_cotangent(golden):
-    """backward_impl(g1) + backward_impl(g2) = backward_impl(g1 + g2) to fp32 rounding (tests/test_u2fusion_gpu.py's check and bound)."""
-    net = _net(golden)
-    i1, i2, cot = _inputs(golden, "1x19x18")
-    tape = {}
-    with torch.no_grad():
-        net.forward_impl(i1, i2, tape=tape)
-        g2 = t(S.make_feature(77, tuple(cot.shape))).to(_dev())
-        r1, r2, r12 = net.backward_impl(cot, tape), net.backward_impl(g2, tape), net.backward_impl(ops.add(cot, g2), tape)
-    for x, y, z in zip(r1, r2, r12):
-        scale = max(1.0, float(z.abs().max()))
-        err = float((x + y - z).abs().max())
-        print("linearity: err %.3e scale %.3e" % (err, scale))
-        assert err <= 1e-4 * scale
+    """backward_impl(g1) + backward_impl(g2) = backward_impl(g1 + g2) to fp32 rounding: within 1e-4 of the largest gradient
+    (tests/baseline_common.py says why)."""
+    C.reverse_pass_is_linear_in_the_cotangent(_net(golden), *_inputs(golden, "1x19x18"), rtol=1e-4)
 
 
 def test_two_runs_are_bit_identical(golden):
-    net = _net(golden)
-    i1, i2, cot = _inputs(golden, "2x24x32")
-    runs = []
-    with torch.no_grad():
-        for _ in range(2):
-            tape = {}
-            f = net.forward_impl(i1, i2, tape=tape)
-            runs.append([f] + _flat(tape) + list(net.backward_impl(cot, tape)))
-    for x, y in zip(*runs):
-        assert torch.equal(x, y)
+    C.two_runs_are_bit_identical(_net(golden), *_inputs(golden, "2x24x32"), taped=_flat)
 
 
 def test_channel_slices_are_taken_without_a_copy(golden):
     """The composite hands over ir[:, 0:1] and ycc of multi-channel tensors: planes addressed through their batch stride.  forward itself
     takes image_vis[:, :1] of any channel count."""
     net = _net(golden)
-    i1, i2, cot = _inputs(golden, "2x24x32")
-    wide1 = torch.cat([i1, i1 * 0.5, i1 * 0.25], 1).contiguous()
-    wide2 = torch.cat([i2, i2 * 0.5], 1).contiguous()
+    fa, wide1, wide2 = C.channel_slices_are_taken_without_a_copy(net, *_inputs(golden, "2x24x32"))
     with torch.no_grad():
-        ta, tb = {}, {}
-        fa = net.forward_impl(i1, i2, tape=ta)
-        fb = net.forward_impl(wide1, wide2, tape=tb)
-        assert torch.equal(fa, fb)
-        assert torch.equal(fa, net(wide1[:, 0:1], wide2[:, 0:1]))
         assert torch.equal(fa, net(wide1, wide2[:, 0:1]))
-        for x, y in zip(net.backward_impl(cot, ta), net.backward_impl(cot, tb)):
-            assert torch.equal(x, y)
 
 
 def test_settings_that_do_not_apply_change_nothing(golden):
     """One arithmetic: the storage mode, the conv / GEMM precision and two_stream leave every bit where it is."""
-    net = _net(golden)
-    i1, i2, cot = _inputs(golden, "1x13x17")
-    with torch.no_grad():
-        tape = {}
-        base = (net.forward_impl(i1, i2, tape=tape),) + tuple(net.backward_impl(cot, tape))
-    old = dict(ops.CONFIG)
-    try:
-        for storage, conv, gemm, two in (("bf16", "f32", "f32", True), ("f16", "bf16x3", "bf16x3", False)):
-            ops.set_storage(storage), ops.set_conv_precision(conv), ops.set_gemm_precision(gemm)
-            ops.CONFIG["two_stream"] = two
-            with torch.no_grad():
-                tape = {}
-                got = (net.forward_impl(i1, i2, tape=tape),) + tuple(net.backward_impl(cot, tape))
-            assert all(x.dtype == torch.float32 for x in _flat(tape)[:-4])
-            for x, y in zip(base, got):
-                assert torch.equal(x, y)
-    finally:
-        ops.set_storage(old["storage"]), ops.set_conv_precision(old["conv_precision"]), ops.set_gemm_precision(old["gemm_precision"])
-        ops.CONFIG["two_stream"] = old["two_stream"]
+    C.settings_that_do_not_apply_change_nothing(_net(golden), *_inputs(golden, "1x13x17"), fp32_maps=lambda tape: _flat(tape)[:-4])
 
 
 def test_wrong_planes_are_refused_on_the_device(golden):
     net = _net(golden)
-    z = torch.zeros(1, 1, 8, 8, device=_dev())
+    z = torch.zeros(1, 1, 8, 8, device=dev())
     with pytest.raises(TypeError, match="fp32"):
         net(z.half(), z.half())
     with pytest.raises(ValueError, match=r"\[B,1,H,W\]"):
-        net(z, torch.zeros(1, 1, 8, 9, device=_dev()))
+        net(z, torch.zeros(1, 1, 8, 9, device=dev()))
     with pytest.raises(ValueError, match=r"\[B,1,H,W\]"):                      # image_ir has one channel
-        net(torch.zeros(1, 3, 8, 8, device=_dev()), torch.zeros(1, 3, 8, 8, device=_dev()))
+        net(torch.zeros(1, 3, 8, 8, device=dev()), torch.zeros(1, 3, 8, 8, device=dev()))
     trainable = _net(golden).requires_grad_(True)
     with pytest.raises(NotImplementedError, match="[Pp]arameter gradients"):
         trainable(z, z)
@@ -358,8 +279,8 @@ def test_reference_initialisation_matches_torch_eager(golden):
     from paif_amd.fusion_model.seafusion import SeaFusion
 
     torch.manual_seed(20)
-    net = SeaFusion().eval().requires_grad_(False).to(_dev())
-    sob = torch.tensor([[1., 0., -1.], [2., 0., -2.], [1., 0., -1.]], device=_dev())
+    net = SeaFusion().eval().requires_grad_(False).to(dev())
+    sob = torch.tensor([[1., 0., -1.], [2., 0., -2.], [1., 0., -1.]], device=dev())
     assert torch.equal(net.vis_rgbd2.sobelconv.convx.weight, sob.expand(32, 1, 3, 3))
     assert torch.equal(net.inf_rgbd1.sobelconv.convy.weight, sob.t().expand(16, 1, 3, 3))
     i1, i2, _ = _inputs(golden, "1x13x17")
@@ -372,160 +293,35 @@ def test_reference_initialisation_matches_torch_eager(golden):
 
 
 # ---- inside the composite model ------------------------------------------------------------------------------------------------
-@pytest.fixture
-def exact_arithmetic():
-    """The setting tests/test_attack_gpu.py asserts gradient parity under: exact-fp32 conv and GEMM kernels."""
-    old, oldg = ops.CONFIG["conv_precision"], ops.CONFIG["gemm_precision"]
-    ops.set_conv_precision("f32")
-    ops.set_gemm_precision("f32")
-    yield
-    ops.set_conv_precision(old)
-    ops.set_gemm_precision(oldg)
-
-
-def _composite(golden):
-    """As tests/test_u2fusion_gpu.py:_composite, with SeaFusion as the fusion module; its weights are the fixture's."""
-    from paif_amd.core.model_fusion_auto import Network_MM_CompModel
+def _in_composite(golden):
+    """The network with the fixture's weights as the fusion module of Network_MM_CompModel."""
     from paif_amd.fusion_model.seafusion import SeaFusion
 
-    m = Network_MM_CompModel(SeaFusion(), None, None, "mit_b0", num_classes=9).eval()
-    S.load_formula_weights(m, head=Hh.HEAD64["mit_b0"])
-    m.enhance_net.load_state_dict(_sd(golden), strict=True)
-    return m.to(_dev())
-
-
-def _batch(start=0):
-    ir, vis, lab = S.make_batch(2, 64, 96, start=start)
-    return t(ir).to(_dev()), t(vis).to(_dev()), t(lab).to(_dev())
-
-
-def _scale(a):
-    return max(1.0, float(np.abs(a).max()))
+    return C.composite(SeaFusion(), _sd(golden))
 
 
 def test_composite_clean_forward(golden):
-    """Tolerances of tests/test_u2fusion_gpu.py::test_composite_clean_forward: fused 1e-4, logits 2e-4 x scale, argmax agreement 99.9 %."""
+    """fused within 1e-4, logits within 2e-4 x scale, argmax agreement 99.9 %: the tolerances of
+    tests/test_seg_gpu.py::test_full_model_config1_4x64x96."""
     g = golden("gs_seafusion_attack")
-    m = _composite(golden)
-    ir, vis, lab = _batch(int(g["start"]))
-    with torch.no_grad():
-        fused, seg = m(ir, vis)
-    print("composite: fused err %.3e logits err %.3e (scale %.3e)" % (maxabs(fused.cpu(), g["fused"]), maxabs(seg.cpu(), g["logits"]),
-                                                                    _scale(g["logits"])))
-    assert maxabs(fused.cpu(), g["fused"]) <= 1e-4
-    assert maxabs(seg.cpu(), g["logits"]) <= 2e-4 * _scale(g["logits"])
-    up = torch.nn.functional.interpolate(seg.cpu(), size=lab.shape[1:], mode="bilinear", align_corners=False)
-    agree = (up.argmax(1).numpy() == g["pred"]).mean()
-    print("composite: argmax agreement %.5f" % agree)
-    assert agree >= 0.999
-
-
-def _check_attack(g, d_ir, d_vis, trace, loss_rtol, frac):
-    """tests/test_attack_gpu.py:_check_attack."""
-    losses = np.array([s["loss"] for s in trace])
-    np.testing.assert_allclose(losses, g["losses"], rtol=loss_rtol)
-    for mine, ref in ((trace[-1]["g_ir"], g["gsum_ir"]), (trace[-1]["g_vis"], g["gsum_vis"])):
-        mism = (np.sign(mine.cpu().numpy()) != np.sign(ref)).mean()
-        print("attack: sign mismatch of the running sum %.2e" % mism)
-        assert mism <= frac
-    for mine, ref in ((d_ir, g["delta_ir"]), (d_vis, g["delta_vis"])):
-        a = mine.detach().cpu().numpy()
-        diff = (np.abs(a - ref) > 1e-6).mean()
-        print("attack: share of differing delta elements %.2e" % diff)
-        assert diff <= frac
-        assert np.abs(a).max() <= 8 / 255. + 1e-7
+    C.composite_clean_forward(_in_composite(golden), g, start=int(g["start"]), fused_atol=1e-4, logits_rtol=2e-4, agreement=0.999)
 
 
 def test_attack_both_pgd_through_the_baseline(golden, exact_arithmetic):
-    from paif_amd.attack.attack import attack_both
-
+    """Losses rtol 1e-4, sign and delta mismatch <= 2e-3, against the reference's float32 trace."""
     g = golden("gs_seafusion_attack")
-    m = _composite(golden)
-    assert hasattr(m, "forward_taped")                       # the fast path of attack.py is the one taken
-    ir, vis, lab = _batch(int(g["start"]))
-    trace = []
-    with torch.no_grad():
-        d_ir, d_vis = attack_both(m, vis, ir, lab, epsilon=EPS, alpha=ALPHA, attack_iters=3, attack_loss='l_seg', attack_way='PGD',
-                                  delta0_ir=t(g["d0_ir"]), delta0_vis=t(g["d0_vis"]), trace=trace)
-    for s in trace:
-        assert s["g_ir"].grad_fn is None and s["g_vis"].grad_fn is None and not s["g_ir"].requires_grad
-    print("attack: losses %s reference %s" % ([s["loss"] for s in trace], list(g["losses"])))
-    _check_attack(g, d_ir, d_vis, trace, 1e-4, 2e-3)
-
-
-def _pgd_iterations(m, ir, vis, lab64, d_ir, d_vis, g_ir, g_vis, gs, iters):
-    """The fast path of attack.py:_attack_loop, in place on d_*, g_* (so that it can be captured)."""
-    for i in range(iters):
-        with ops.attack_forward_arithmetic():
-            _, logits, tape = m.forward_taped(ops.add(ir, d_ir), ops.add(vis, d_vis))
-        way, wt, wf = ops.attack_loss_weights('PGD', i, iters)
-        coef = ops.attack_loss_fwd(logits, lab64, way, wt, wf)
-        d32 = ops.attack_loss_bwd(logits, lab64, coef, way, wt, wf, upstream=gs)
-        with ops.attack_backward_arithmetic():
-            gi, gv = m.backward_taped(d32, tape)
-        ops.axpy_(g_ir, gi.contiguous(), 1.0 / gs)
-        ops.pgd_step_(d_ir, g_ir, ir, ALPHA, EPS)
-        ops.axpy_(g_vis, gv.contiguous(), 1.0 / gs)
-        ops.pgd_step_(d_vis, g_vis, vis, ALPHA, EPS)
+    C.attack_both_pgd(_in_composite(golden), g, start=int(g["start"]), eps=EPS, alpha=ALPHA, loss_rtol=1e-4, frac=2e-3)
 
 
 def test_pgd_iterations_replayed_from_a_graph_are_bit_identical(golden):
     """Three PGD iterations captured once with torch.cuda.graph and replayed = the eager loop.  Single stream, no parallel branches; every
     weight pack is built before the capture."""
     g = golden("gs_seafusion_attack")
-    m = _composite(golden)
-    ir, vis, lab = _batch(int(g["start"]))
-    lab64 = lab.type(torch.long).contiguous()
-    d0_ir, d0_vis = t(g["d0_ir"]).to(_dev()), t(g["d0_vis"]).to(_dev())
-    state = [torch.zeros_like(x) for x in (ir, vis, ir, vis)]
-
-    def reset():
-        state[0].copy_(d0_ir), state[1].copy_(d0_vis), state[2].zero_(), state[3].zero_()
-
-    gstream = torch.cuda.Stream()
-    graph = torch.cuda.CUDAGraph()
-    with torch.no_grad(), ops.attack_arithmetic():
-        gs = ops.attack_grad_scale(lab64)
-        reset()
-        _pgd_iterations(m, ir, vis, lab64, *state, gs, 3)     # eager: also builds every weight pack outside the capture
-        eager = [x.clone() for x in state]
-        torch.cuda.synchronize()
-        with torch.cuda.stream(gstream):
-            reset()
-            _pgd_iterations(m, ir, vis, lab64, *state, gs, 3)
-            torch.cuda.synchronize()
-            with torch.cuda.graph(graph, stream=gstream):
-                _pgd_iterations(m, ir, vis, lab64, *state, gs, 3)
-        torch.cuda.synchronize()
-        reset()
-        torch.cuda.synchronize()
-        graph.replay()
-        torch.cuda.synchronize()
-    assert float(eager[2].abs().max()) > 0
-    for x, y in zip(eager, state):
-        assert torch.equal(x, y)
+    C.pgd_iterations_replayed_from_a_graph_are_bit_identical(_in_composite(golden), start=int(g["start"]),
+                                                             delta0=lambda ir, vis: (t(g["d0_ir"]), t(g["d0_vis"])), eps=EPS, alpha=ALPHA)
 
 
 def test_robustness_harnesses_run_with_the_baseline(golden):
     """val_segformer_robust2 (clean) and val_segformer_robust (PGD, 2 iterations) on two 2x64x96 batches: finite mIoU, and the clean one is
     what the confusion matrix of the model's own seg_map argmax gives."""
-    from oracle import paif_oracle as O
-    from paif_amd.harness import val_segformer_robust, val_segformer_robust2
-
-    m = _composite(golden)
-    batches = []
-    for start in (0, 2):
-        ir, vis, lab = _batch(start)
-        batches.append((vis, ir, lab))
-    clean = val_segformer_robust2(m, batches)
-    conf = np.zeros((9, 9), dtype=np.int64)
-    with torch.no_grad():
-        for vis, ir, lab in batches:
-            _, seg = m(ir, vis)
-            up = torch.nn.functional.interpolate(seg.cpu(), size=lab.shape[1:], mode="bilinear", align_corners=False)
-            conf += O.confusion_matrix(lab.cpu().numpy(), up.argmax(1).numpy())
-    iou = O.compute_results(conf)[2]
-    assert np.isfinite(clean["miou"])
-    assert abs(clean["miou"] - float(np.mean(np.nan_to_num(iou)))) <= 1e-12
-    rob = val_segformer_robust(m, batches, attack_iters=2)
-    assert np.isfinite(rob["miou"])
+    C.robustness_harnesses_run(_in_composite(golden), miou_atol=1e-12, attack_iters=2)
