@@ -721,6 +721,41 @@ int paif_ssim_l1_fwd(const float* x, const float* y, const float* window1d, floa
 int paif_ssim_l1_bwd_input(const float* x, const float* y, const float* window1d, const float* k, float* abc_scratch,
                            float* dx, int B, int H, int W, paif_stream_t stream);
 
+/* ---- Sobel fusion criteria (core/loss.py:423-474, 516-571, 595-603) and the Sobelxy operator (core/loss.py:634-650) ---------
+ * S(x) = |Gx * x| + |Gy * x|: the 3x3 Sobel pair as cross-correlations, zero padding 1, every image padded on its own.
+ * A criterion = t_weight[0] * mean|T0 - f| + t_weight[1] * mean|T1 - f| + q_weight * mean|Q - S(f)| on fp32 planes [B,1,H,W]:
+ * f the generated plane, a = infrared channel 0, b = Y, m = mask channel 0, each a pointer to image 0 plus a batch stride in
+ * floats (rows dense), so a channel of a wider tensor is read in place.  Kind of a target:
+ *   MAX:  T = max(a, b)           Q = max(S(a), S(b))             (Fusionloss :432-438, Fusionloss6 :532, Fusionloss_add :568)
+ *   MASK: T = m                   Q = S(m)                        (Fusionloss2 :450, Fusionloss3 :468-473, Fusionloss6 :525)
+ *   LIN:  T = alpha*a + beta*b    Q = S(alpha*a + beta*b)         (Fusionloss4 :546-550, Fusionloss6 :530, Fusionloss_add :564)
+ * NONE switches a term off.  Planes no term reads may be NULL. */
+#define PAIF_SOBEL_NONE 0
+#define PAIF_SOBEL_MAX 1
+#define PAIF_SOBEL_MASK 2
+#define PAIF_SOBEL_LIN 3
+typedef struct {
+  const float *f, *a, *b, *m;
+  size_t f_bs, a_bs, b_bs, m_bs;
+  int t_kind[2];
+  float t_alpha[2], t_beta[2], t_weight[2];
+  int q_kind;
+  float q_alpha, q_beta, q_weight;
+} paif_sobel_desc;
+/* partial: 3 * paif_sobel_loss_blocks(B, H, W) floats of scratch (-1: the batch has more tiles than a 32-bit block index).
+ * out[4] (device) = the three means and their weighted sum, reduced on the device in block order in double: the same inputs give
+ * the same bits.  Two launches, no host synchronisation, no allocation: capturable.  Any H, W >= 1. */
+int paif_sobel_loss_blocks(int B, int H, int W);
+int paif_sobel_loss_fwd(const paif_sobel_desc* d, float* partial, float* out, int B, int H, int W, paif_stream_t stream);
+/* df [B,1,H,W] (dense) = g[0] * d(weighted sum)/df, g: 1 device float (the upstream gradient):
+ * df = -sum_i k_i sign(T_i - f) + Gx^T(e sign(Gx f)) + Gy^T(e sign(Gy f)), e = -k_q sign(Q - S(f)), k = g[0] * weight / (B*H*W),
+ * sign(0) = 0 (torch's abs / l1_loss).  One launch.  The gradients w.r.t. a, b, m are not built. */
+int paif_sobel_loss_bwd(const paif_sobel_desc* d, const float* g, float* df, int B, int H, int W, paif_stream_t stream);
+/* Sobelxy.forward (core/loss.py:647-650) as a map: out [B,1,H,W] (dense) = S(x); x: plane pointer + batch stride in floats.
+ * bwd: dx (dense) = Gx^T(g sign(Gx x)) + Gy^T(g sign(Gy x)) for the cotangent map g [B,1,H,W] (dense). */
+int paif_sobelxy_fwd(const float* x, size_t x_bs, float* out, int B, int H, int W, paif_stream_t stream);
+int paif_sobelxy_bwd(const float* x, size_t x_bs, const float* g, float* dx, int B, int H, int W, paif_stream_t stream);
+
 /* ---- SegFormerHead with linear_fuse folded in front of the upsampling (core/segformer_head.py:63-80) ------------------------------
  * conv1x1(cat[up y4, up y3, up y2, y1]) = up(W4 y4) + up(W3 y3) + up(W2 y2) + W1 y1 (both maps are linear): z_i = W_i y_i are
  * GEMMs at each stage's own resolution; this kernel forms relu((z1 + up z2 + up z3 + up z4) * scale + shift) at 1/4 resolution.

@@ -25,6 +25,16 @@ class ConvDesc(Structure):
     ]
 
 
+class SobelDesc(Structure):
+    """paif_sobel_desc (include/paif_hip.h)."""
+
+    _fields_ = [
+        ("f", F), ("a", F), ("b", F), ("m", F), ("f_bs", c_size_t), ("a_bs", c_size_t), ("b_bs", c_size_t), ("m_bs", c_size_t),
+        ("t_kind", c_int * 2), ("t_alpha", c_float * 2), ("t_beta", c_float * 2), ("t_weight", c_float * 2),
+        ("q_kind", c_int), ("q_alpha", c_float), ("q_beta", c_float), ("q_weight", c_float),
+    ]
+
+
 # name -> (restype, argtypes); every symbol declared in include/paif_hip.h
 SIGNATURES = {
     "paif_version": (c_int, []),
@@ -114,6 +124,11 @@ SIGNATURES = {
     "paif_ssim_l1_blocks": (c_int, [c_int, c_int, c_int]),
     "paif_ssim_l1_fwd": (c_int, [F, F, F, F, F, c_int, c_int, c_int, F]),
     "paif_ssim_l1_bwd_input": (c_int, [F, F, F, F, F, F, c_int, c_int, c_int, F]),
+    "paif_sobel_loss_blocks": (c_int, [c_int, c_int, c_int]),
+    "paif_sobel_loss_fwd": (c_int, [POINTER(SobelDesc), F, F, c_int, c_int, c_int, F]),
+    "paif_sobel_loss_bwd": (c_int, [POINTER(SobelDesc), F, F, c_int, c_int, c_int, F]),
+    "paif_sobelxy_fwd": (c_int, [F, c_size_t, F, c_int, c_int, c_int, F]),
+    "paif_sobelxy_bwd": (c_int, [F, c_size_t, F, F, c_int, c_int, c_int, F]),
     "paif_gemm_splitk_fwd": (c_int, [F, c_int, F, F, F, c_int, F, c_int, F, c_int, c_int, c_int, c_int, c_int, F, F]),
     "paif_gemm_splitk_fwd_p": (c_int, [F, c_int, F, F, F, c_int, F, c_int, F, c_int, c_int, c_int, c_int, c_int, F, c_int, F]),
     "paif_layernorm_fwd": (c_int, [F, F, F, F, c_int, c_int, c_float, F]),

@@ -4,7 +4,16 @@
 
 Built: the forward value and the gradient w.r.t. the generated image (HIP kernels paif_ssim_l1_fwd / _bwd_input), so the loss
 can sit on top of the models' input-gradient autograd nodes.  Not built: parameter gradients -- the training step (BASELINE
-config 5: wgrad kernels, AdamW kernels, RCCL gradient all-reduce) is outside round 1.  A `mask` that requires grad raises."""
+config 5: wgrad kernels, AdamW kernels, RCCL gradient all-reduce) is outside round 1.  A `mask` that requires grad raises.
+
+The Sobel criteria of core/loss.py:423-474, 516-571, 595-603 -- `Fusionloss` (max intensity + max Sobel gradient), `Fusionloss2/3/4/6`,
+`Fusionloss_add`, `Total_fusion_loss3` -- and the `Sobelxy` operator (:634-650) run on csrc/sobel_loss.hip: one launch (plus a one-block
+finish) reads each plane once and gives the value as a 0-d device tensor, one launch gives d/d(generated image); channel 0 of `ir`, `vis`
+and `mask` is read in place.  `Fusionloss_grad3` (:504-515) is MSE + 1.1 * (1 - SSIM) on the existing kernels.  Every criterion is
+differentiable w.r.t. the generated image only: `ir`, `vis` or `mask` requiring grad under recording autograd raises NotImplementedError.
+A class that reads its image arguments says so with `reads_images = True`; the composite models then refuse `ir` / `vis` that require
+grad in their `_loss*` methods instead of dropping the criterion's direct image term.  Not built: `new_loss_sobel`,
+`Total_fusion_loss`, `Total_fusion_loss2`, `IQALoss` / `Entropy`, `Fusionloss_grad`, and the segmentation / FCOS criteria."""
 import torch
 import torch.nn as nn
 
@@ -53,3 +62,120 @@ class Fusionloss_grad2(nn.Module):
 
     def forward(self, image_ir, image_vis, generate_img, mask):
         return _ssim_l1(generate_img, mask[:, :1, :, :], 1.0, 1.1)
+
+
+class Fusionloss_grad3(nn.Module):
+    """core/loss.py:504-515: MSE(mask, gen) + 1.1 * (1 - ssim(gen, mask)) on the MSE (ops.image_loss) and SSIM kernels.  The reference's
+    constructor also builds a LapLoss2 it never calls; that third-party module is absent here and nothing is constructed."""
+
+    def __init__(self):
+        super().__init__()
+
+    def forward(self, image_ir, image_vis, generate_img, mask):
+        mask = mask[:, :1, :, :]
+        if torch.is_grad_enabled() and mask.requires_grad:
+            raise NotImplementedError("Fusionloss_grad3: the gradient w.r.t. the mask is not built")
+        _check_gen(generate_img, mask, "mask")
+        return ops.image_loss(generate_img, mask, "l_2") + _ssim_l1(generate_img, mask, 0.0, 1.1)
+
+
+def _check_gen(gen, other, name):
+    if gen.dtype != torch.float32 or other.dtype != torch.float32:
+        raise TypeError("expected float32, got %s (generated image) and %s (%s)" % (gen.dtype, other.dtype, name))
+    if gen.dim() != 4 or gen.shape[1] != 1 or tuple(other.shape) != tuple(gen.shape):
+        raise ValueError("expected the generated image and %s as one shape [B,1,H,W], got %s and %s" % (name, tuple(gen.shape), tuple(other.shape)))
+    if not (gen.is_cuda and other.is_cuda):
+        raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got %s (generated image) and %s (%s) -- there is no CPU path"
+                           % (gen.device, other.device, name))
+
+
+class Sobelxy(nn.Module):
+    """core/loss.py:634-650: |Gx * x| + |Gy * x| of a 1-channel map, zero padding 1 (ops.sobelxy: value and input gradient).  weightx /
+    weighty keep the reference's surface and are not read by the kernels; they are plain tensors, so state_dict() is empty -- as in
+    the reference on a GPU, where `.cuda()` on the Parameter leaves a tensor that the module does not register."""
+
+    def __init__(self):
+        super().__init__()
+        self.weightx = torch.tensor([[-1., 0., 1.], [-2., 0., 2.], [-1., 0., 1.]]).unsqueeze(0).unsqueeze(0)
+        self.weighty = torch.tensor([[1., 2., 1.], [0., 0., 0.], [-1., -2., -1.]]).unsqueeze(0).unsqueeze(0)
+
+    def forward(self, x):
+        return ops.sobelxy(x)
+
+
+class _SobelCriterion(nn.Module):
+    """One launch for the value, one for d/d(generated image): the term table of ops.sobel_loss.  `self.sobelconv` as in the reference."""
+
+    def __init__(self):
+        super().__init__()
+        self.sobelconv = Sobelxy()
+
+
+_MAX, _MASK, _LIN = ops.SOBEL_MAX, ops.SOBEL_MASK, ops.SOBEL_LIN
+
+
+class Fusionloss(_SobelCriterion):
+    """core/loss.py:423-440 (SeAFusion's loss): L1(max(y, ir), gen) + 8 * L1(max(S y, S ir), S gen)."""
+
+    reads_images = True   # the composite models must not detach ir / vis in front of this criterion: see _CompositeBase._refuse_image_grads
+    criterion_args = ("ir", "vis", "gen")   # no mask: the composite models call the criterion by this order (_CompositeBase._call_criterion)
+
+    def forward(self, image_ir, image_vis, generate_img):
+        return ops.sobel_criterion(generate_img, image_ir, image_vis, None, [(_MAX, 1.0, 0.0, 0.0)], (_MAX, 8.0, 0.0, 0.0))
+
+
+class Fusionloss2(_SobelCriterion):
+    """core/loss.py:441-457: L1(mask, gen)."""
+
+    def forward(self, image_ir, image_vis, generate_img, mask):
+        return ops.sobel_criterion(generate_img, None, None, mask, [(_MASK, 1.0, 0.0, 0.0)], None)
+
+
+class Fusionloss3(_SobelCriterion):
+    """core/loss.py:459-474: L1(mask, gen) + L1(S mask, S gen)."""
+
+    def forward(self, image_ir, image_vis, generate_img, mask):
+        return ops.sobel_criterion(generate_img, None, None, mask, [(_MASK, 1.0, 0.0, 0.0)], (_MASK, 1.0, 0.0, 0.0))
+
+
+class Fusionloss6(_SobelCriterion):
+    """core/loss.py:516-535: 0.5 * L1(mask, gen) + 0.5 * L1(y + ir, gen) + 6 * L1(max(S y, S ir), S gen)."""
+
+    reads_images = True
+
+    def forward(self, image_ir, image_vis, generate_img, mask):
+        return ops.sobel_criterion(generate_img, image_ir, image_vis, mask, [(_MASK, 0.5, 0.0, 0.0), (_LIN, 0.5, 1.0, 1.0)],
+                                   (_MAX, 6.0, 0.0, 0.0))
+
+
+class Fusionloss4(_SobelCriterion):
+    """core/loss.py:537-552: syn = (y + ir) / 2; L1(syn, gen) + 4 * L1(S syn, S gen).  The mask is not read."""
+
+    reads_images = True
+
+    def forward(self, image_ir, image_vis, generate_img, mask):
+        return ops.sobel_criterion(generate_img, image_ir, image_vis, None, [(_LIN, 1.0, 0.5, 0.5)], (_LIN, 4.0, 0.5, 0.5))
+
+
+class Fusionloss_add(_SobelCriterion):
+    """core/loss.py:554-571: 1.5 * L1(0.4 * y + 0.6 * ir, gen) + 5 * L1(max(S y, S ir), S gen)."""
+
+    reads_images = True
+    criterion_args = ("ir", "vis", "gen")
+
+    def forward(self, image_ir, image_vis, generate_img):
+        return ops.sobel_criterion(generate_img, image_ir, image_vis, None, [(_LIN, 1.5, 0.6, 0.4)], (_MAX, 5.0, 0.0, 0.0))
+
+
+class Total_fusion_loss3(nn.Module):
+    """core/loss.py:595-603: 3 * Fusionloss(ir, vis, gen).  Note the argument order: the mask comes third and is not read."""
+
+    reads_images = True
+    criterion_args = ("ir", "vis", "mask", "gen")
+
+    def __init__(self):
+        super().__init__()
+        self.fl = Fusionloss()
+
+    def forward(self, image_ir, image_vis, mask, generate_img):
+        return ops.sobel_criterion(generate_img, image_ir, image_vis, None, [(_MAX, 3.0, 0.0, 0.0)], (_MAX, 24.0, 0.0, 0.0))

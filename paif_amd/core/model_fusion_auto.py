@@ -783,24 +783,44 @@ class _CompositeBase(nn.Module):
     def _ycc(vis):
         return ops.rgb2ycrcb(vis.detach())   # the criterion ignores its image arguments (core/loss.py:494-502)
 
+    def _refuse_image_grads(self, ir, vis):
+        """Fusionloss_grad2 ignores its images, so `_ycc` detaches `vis`; a criterion that reads them (`reads_images = True`: the Sobel
+        criteria) has a direct image term whose gradient is not built -- refuse rather than drop it."""
+        if getattr(self._criterion, "reads_images", False) and torch.is_grad_enabled() and (ir.requires_grad or vis.requires_grad):
+            raise NotImplementedError("%s reads its image arguments and its gradient w.r.t. image_ir / image_vis is not built: ir / vis "
+                                      "must not require grad in the composite models' loss methods" % type(self._criterion).__name__)
+
+    def _call_criterion(self, ir, ycc, fused_img, mask):
+        """self._criterion(ir, ycc, fused_img, mask), the reference's call (:1097).  Three criteria of core/loss.py take other arguments
+        (Fusionloss / Fusionloss_add: no mask; Total_fusion_loss3: the mask third) -- under the reference's call the first two raise a
+        TypeError and the third swaps mask and image silently.  They name their order in `criterion_args` and are called by it."""
+        order = getattr(self._criterion, "criterion_args", None)
+        if order is None:
+            return self._criterion(ir, ycc, fused_img, mask)
+        return self._criterion(*[dict(ir=ir, vis=ycc, gen=fused_img, mask=mask)[k] for k in order])
+
     def _loss(self, ir, vis, mask, labels):
+        self._refuse_image_grads(ir, vis)
         fused_img, seg_map = self(ir, vis)
-        enhance_loss = self._criterion(ir, self._ycc(vis), fused_img, mask)
+        enhance_loss = self._call_criterion(ir, self._ycc(vis), fused_img, mask)
         return enhance_loss * 0.1 + self._seg_term(seg_map, labels) * 4
 
     def _loss_coupled(self, ir_, vis_, mask, labels):
+        self._refuse_image_grads(ir_[1], vis_[1])
         fused_img, seg_map = self(ir_[0], vis_[0])
         denoise_loss = self._seg_term(seg_map, labels)
-        enhance_loss = self._criterion(ir_[1], self._ycc(vis_[1]), fused_img, mask)
+        enhance_loss = self._call_criterion(ir_[1], self._ycc(vis_[1]), fused_img, mask)
         return enhance_loss * 0.1 + denoise_loss * 4
 
     def _fusion_loss_lower(self, ir, vis, mask):
+        self._refuse_image_grads(ir, vis)
         fused_img, _ = self(ir, vis)
-        return self._criterion(ir, self._ycc(vis), fused_img, mask)
+        return self._call_criterion(ir, self._ycc(vis), fused_img, mask)
 
     def _fusion_loss(self, ir, vis, mask):
+        self._refuse_image_grads(ir, vis)
         fused_img = self.forward_fusion(ir, vis)
-        return self._criterion(ir, self._ycc(vis), fused_img, mask)
+        return self._call_criterion(ir, self._ycc(vis), fused_img, mask)
 
     _fusion_loss_wogan = _fusion_loss
 

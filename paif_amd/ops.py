@@ -2035,6 +2035,160 @@ def ssim_l1(x, y):
     return s[0], s[1]
 
 
+# ---- Sobel fusion criteria (csrc/sobel_loss.hip; core/loss.py:423-474, 516-571, 595-603, 634-650) ----
+SOBEL_NONE, SOBEL_MAX, SOBEL_MASK, SOBEL_LIN = 0, 1, 2, 3
+
+
+def _check_plane0(t, shape, name):
+    """dtype and shape of a plane argument (before any device check, so that a wrong argument is named as such on any device)."""
+    if t is None:
+        return
+    if t.dtype != torch.float32:
+        raise TypeError("%s: expected float32, got %s" % (name, t.dtype))
+    B, _, H, W = shape
+    if t.dim() != 4 or t.shape[1] < 1 or (t.shape[0], t.shape[2], t.shape[3]) != (B, H, W):
+        raise ValueError("%s: expected [%d, C >= 1, %d, %d] like the generated image, got %s" % (name, B, H, W, tuple(t.shape)))
+
+
+def _plane0(t, shape, name):
+    """Channel 0 of a [B,C,H,W] fp32 device tensor as (keep-alive tensor, pointer, batch stride in floats), read in place when the
+    channel's rows are dense; `shape` = the generated image's [B,1,H,W]."""
+    if t is None:
+        return None, None, 0
+    _check_plane0(t, shape, name)
+    if not t.is_cuda:
+        raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor for %s -- there is no CPU path" % (t.device, name))
+    B, _, H, W = shape
+    t = t.detach()
+    if not ((W == 1 or t.stride(3) == 1) and (H == 1 or t.stride(2) == W) and (B == 1 or t.stride(0) >= H * W)):
+        t = t[:, :1].contiguous()
+    return t, ctypes.c_void_p(t.data_ptr()), (t.stride(0) if B > 1 else H * W)
+
+
+def _sobel_desc(gen, ir, y, mask, intensity, gradient):
+    """intensity: up to two (kind, weight, alpha, beta); gradient: one such tuple or None -> (paif_sobel_desc, tensors kept alive)."""
+    if gen.dtype != torch.float32:
+        raise TypeError("generated image: expected float32, got %s" % gen.dtype)
+    if gen.dim() != 4 or gen.shape[1] != 1:
+        raise ValueError("generated image: expected [B,1,H,W], got %s" % (tuple(gen.shape),))
+    for t, name in ((ir, "image_ir"), (y, "image_vis"), (mask, "mask")):
+        _check_plane0(t, gen.shape, name)
+    if not gen.is_cuda:
+        raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor for the generated image -- there is no CPU path" % gen.device)
+    if len(intensity) > 2:
+        raise ValueError("sobel_loss: at most two intensity terms, got %d" % len(intensity))
+    gen = gen.detach().contiguous()
+    d = _lib.SobelDesc()
+    keep = [gen]
+    d.f, d.f_bs = ctypes.c_void_p(gen.data_ptr()), gen.shape[2] * gen.shape[3]
+    for fld, t, name in (("a", ir, "image_ir"), ("b", y, "image_vis"), ("m", mask, "mask")):
+        tt, ptr, bs = _plane0(t, gen.shape, name)
+        keep.append(tt)
+        setattr(d, fld, ptr)
+        setattr(d, fld + "_bs", bs)
+    for i, (kind, w, al, be) in enumerate(intensity):
+        d.t_kind[i], d.t_weight[i], d.t_alpha[i], d.t_beta[i] = kind, w, al, be
+    if gradient is not None:
+        d.q_kind, d.q_weight, d.q_alpha, d.q_beta = gradient
+    return d, keep
+
+
+def sobel_loss(gen, ir, y, mask, intensity, gradient):
+    """sum_i w_i mean|T_i - gen| + w_q mean|Q - S(gen)|  (include/paif_hip.h: paif_sobel_desc) on channel 0 of ir / y / mask (None where
+    no term reads it) -> device tensor [4]: the means of the two intensity terms and of the gradient term, and the weighted sum.
+    Forward value only; no host synchronisation."""
+    d, keep = _sobel_desc(gen, ir, y, mask, intensity, gradient)
+    B, _, H, W = gen.shape
+    L = lib()
+    nblk = L.paif_sobel_loss_blocks(B, H, W)
+    if nblk <= 0:
+        raise ValueError("sobel_loss: a batch of %d x %d x %d planes is empty or has more tiles than a 32-bit block index" % (B, H, W))
+    partial = torch.empty((nblk, 3), device=gen.device, dtype=torch.float32)
+    out = torch.empty(4, device=gen.device, dtype=torch.float32)
+    _lib.check(L.paif_sobel_loss_fwd(ctypes.byref(d), _p(partial), _p(out), B, H, W, _stream()), "sobel_loss")
+    return out
+
+
+def sobel_loss_bwd(gen, ir, y, mask, intensity, gradient, g):
+    """g (0-d or 1-element fp32 device tensor: the upstream gradient) -> g * d sobel_loss[3] / d gen, [B,1,H,W]; sign(0) = 0."""
+    d, keep = _sobel_desc(gen, ir, y, mask, intensity, gradient)
+    B, _, H, W = gen.shape
+    df = torch.empty((B, 1, H, W), device=gen.device, dtype=torch.float32)
+    g = g.detach().reshape(1).to(torch.float32).contiguous()
+    _lib.check(lib().paif_sobel_loss_bwd(ctypes.byref(d), _p(g), _p(df), B, H, W, _stream()), "sobel_loss_bwd")
+    return df
+
+
+class SobelLoss(torch.autograd.Function):
+    """The weighted sum of sobel_loss as a 0-d tensor, differentiable w.r.t. the generated image only."""
+
+    @staticmethod
+    def forward(ctx, gen, ir, y, mask, intensity, gradient):
+        out = sobel_loss(gen, ir, y, mask, intensity, gradient)
+        ctx.save_for_backward(*[t.detach() for t in (gen, ir, y, mask) if t is not None])
+        ctx.have = [t is not None for t in (gen, ir, y, mask)]
+        ctx.terms = (intensity, gradient)
+        return out[3].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        it = iter(ctx.saved_tensors)
+        gen, ir, y, mask = [next(it) if h else None for h in ctx.have]
+        return sobel_loss_bwd(gen, ir, y, mask, ctx.terms[0], ctx.terms[1], g), None, None, None, None, None
+
+
+def sobel_criterion(gen, ir, y, mask, intensity, gradient):
+    """sobel_loss's weighted sum with autograd: the gradient w.r.t. `gen` is built, the one w.r.t. ir / y / mask is refused."""
+    if torch.is_grad_enabled():
+        for t, name in ((ir, "image_ir"), (y, "image_vis"), (mask, "mask")):
+            if t is not None and t.requires_grad:
+                raise NotImplementedError("Sobel fusion criteria: the gradient w.r.t. %s is not built (only the generated image's is)" % name)
+        if gen.requires_grad:
+            return SobelLoss.apply(gen, ir, y, mask, tuple(intensity), gradient)
+    with torch.no_grad():
+        return sobel_loss(gen, ir, y, mask, intensity, gradient)[3].clone()
+
+
+def sobelxy_bwd(x, g):
+    """(x, cotangent map g), both [B,1,H,W] -> dx = Gx^T(g sign(Gx x)) + Gy^T(g sign(Gy x))."""
+    if x.dim() != 4 or x.shape[1] != 1 or g.shape != x.shape:
+        raise ValueError("sobelxy_bwd: expected two [B,1,H,W] maps, got %s and %s" % (tuple(x.shape), tuple(g.shape)))
+    tx, px, bs = _plane0(x, x.shape, "Sobelxy input")
+    B, _, H, W = x.shape
+    g = g.detach().contiguous()
+    dx = torch.empty((B, 1, H, W), device=x.device, dtype=torch.float32)
+    _lib.check(lib().paif_sobelxy_bwd(px, bs, _p(g), _p(dx), B, H, W, _stream()), "sobelxy_bwd")
+    return dx
+
+
+class Sobelxy(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x):
+        ctx.save_for_backward(x.detach())
+        return sobelxy_fwd(x)
+
+    @staticmethod
+    def backward(ctx, g):
+        return sobelxy_bwd(ctx.saved_tensors[0], g)
+
+
+def sobelxy_fwd(x):
+    if x.dim() != 4 or x.shape[1] != 1:
+        raise ValueError("Sobelxy: expected a 1-channel map [B,1,H,W], got %s" % (tuple(x.shape),))
+    tx, px, bs = _plane0(x, x.shape, "Sobelxy input")
+    B, _, H, W = x.shape
+    out = torch.empty((B, 1, H, W), device=x.device, dtype=torch.float32)
+    _lib.check(lib().paif_sobelxy_fwd(px, bs, _p(out), B, H, W, _stream()), "sobelxy")
+    return out
+
+
+def sobelxy(x):
+    """S(x) = |Gx * x| + |Gy * x| of a 1-channel map (core/loss.py:647-650), differentiable w.r.t. x."""
+    if torch.is_grad_enabled() and x.requires_grad:
+        return Sobelxy.apply(x)
+    return sobelxy_fwd(x)
+
+
 def layernorm(x, weight, bias, eps):
     C = x.shape[-1]
     y = torch.empty_like(x)
