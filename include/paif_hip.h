@@ -1129,6 +1129,51 @@ int paif_drdb_dcov_bwd(const float* pack, int block, int k, const float* slab, f
 int paif_drdb_stem_bwd(const float* pack, float slope, const float* slab, const float* d_slab, float* d_ir, float* d_vis, int B, int H, int W,
                        paif_stream_t stream);
 
+/* SKFF, the selective-kernel feature fusion block (core/model_fusion_auto.py:190-224 of the reference, the same class in operations_m.py),
+ * and the rest of Fusion_Network2 (:227-260; csrc/skff.hip, csrc/conv_slab.h).  fp32 throughout, NHWC maps.
+ *   SKFF(64, height, reduction, bias), d = max(int(64 / reduction), 4) <= 64, height 2 or 3: input h is x_h with pixel stride cs_h floats
+ * (a multiple of 4, >= 64: a map may be the first 64 channels of a 224-channel slab; x2 is ignored at height 2).  V goes to channels
+ * [v_off, v_off + 64) of a map of pixel stride v_cs; dV is read with pixel stride dv_cs.  The tape of the gate: a [B][height][64] (the
+ * softmax over the inputs) and z [B][d] (conv_du.0's output: the PReLU branch is read off it, so any slope is allowed).  dS [B][64].
+ * partial: B * paif_skff_blocks(H, W) * 64 floats forward, * height more in reverse.  pack: paif_skff_pack_floats(height, d) floats:
+ * conv_du.0.weight [d][64], its bias [d], fcs.h.weight [height][64][d], their biases [height][64] (zeros where the module has none).
+ *   Fusion_Network2: conv1, DRDB1 and DRDB2 are the paif_drdb_* entry points on a drdb pack whose conv2 / conv21 places stay zero.  Its own
+ * pack: paif_fn2_pack_floats() floats, ZEROED, then three paif_fn2_pack_conv calls (0 conv3, 1 conv4, 2 conv2) in any order.  The PReLU
+ * slope of the head is an argument, >= 0 (the reverse pass reads the branch off the taped f).
+ * No host synchronisation, no allocation: capturable.  Bit-reproducible (no atomics; partial sums per workgroup, finished in one order). */
+size_t paif_skff_pack_floats(int height, int d);
+/* Pool / reduce workgroups per image (512 pixels each). */
+int paif_skff_blocks(int H, int W);
+/* :205-224, three launches: pool (partial sums of sum_h x_h per workgroup), gate (per image: the partials in block order, the mean,
+ * conv_du, the fcs and the softmax in double; WRITES a and z), apply (V = sum_h a_h x_h).  V must not be one of the inputs. */
+int paif_skff_fwd(const float* x0, int cs0, const float* x1, int cs1, const float* x2, int cs2, int height, int d, const float* pack, float slope,
+                  float* partial, float* a, float* z, float* v, int v_cs, int v_off, int B, int H, int W, paif_stream_t stream);
+/* Reverse of :205-224, three launches: reduce (partials of da_h = sum over pixels of dV x_h), gate-reverse (softmax, fcs, PReLU, conv_du
+ * transposed in double; WRITES d_s), apply-reverse (WRITES d_x_h = a_h dV + d_s / (H W) as dense 64-channel maps; a null d_x_h is not
+ * wanted and not written). */
+int paif_skff_bwd(const float* x0, int cs0, const float* x1, int cs1, const float* x2, int cs2, int height, int d, const float* pack, float slope,
+                  const float* a, const float* z, const float* d_v, int dv_cs, float* partial, float* d_s, float* d_x0, float* d_x1, float* d_x2,
+                  int B, int H, int W, paif_stream_t stream);
+size_t paif_fn2_pack_floats(void);
+/* One Conv2d into the kernels' layout.  conv = 0 conv3 (:237), 1 conv4 (:238), 2 conv2 (:233). */
+int paif_fn2_pack_conv(const float* w, const float* b, int conv, float* pack, paif_stream_t stream);
+/* :247 / :249: out [B,H,W,64] = conv 1x1 of the guidance map `in` plus bias, no activation; which = 0: conv3 of [B,H,W,64], 1: conv4 of
+ * [B,H,W,128].  The slab conv at slope 1. */
+int paif_fn2_guide_fwd(const float* pack, int which, const float* in, float* out, int B, int H, int W, paif_stream_t stream);
+/* Reverse of :247 / :249: d_out [B,H,W,64] through the transposed 1x1; WRITES d_in [B,H,W,64 | 128]. */
+int paif_fn2_guide_bwd(const float* pack, int which, const float* d_out, float* d_in, int B, int H, int W, paif_stream_t stream);
+/* :251: f [B,H,W] = PReLU(conv 3x3, pad 1, 64 -> 1 of the dense 64-channel map `in`), before the normalisation. */
+int paif_fn2_head_fwd(const float* pack, float slope, const float* in, float* f, int B, int H, int W, paif_stream_t stream);
+/* Reverse of :251: d_f through the PReLU (branch from the taped f) and the transposed conv; WRITES the dense 64-channel d_in. */
+int paif_fn2_head_bwd(const float* pack, float slope, const float* f, const float* d_f, float* d_in, int B, int H, int W, paif_stream_t stream);
+/* :257-259: out = (x - min x) / (max x - min x) over all n elements, NO clamp (paif_plane_clamp_minmax_* is the clamped form).  partial:
+ * 2 * paif_plane_minmax_nc_blocks(n) floats forward, 4 * in reverse; minmax: the 2 floats (min, max) the reverse pass reads.  Reverse
+ * with torch's semantics: the gradient of an extremum is spread evenly over the elements that attain it.  Two launches each. */
+int paif_plane_minmax_nc_blocks(size_t n);
+int paif_plane_minmax_nc_fwd(const float* x, float* out, float* partial, float* minmax_out, size_t n, paif_stream_t stream);
+int paif_plane_minmax_nc_bwd_input(const float* dout, const float* x, const float* minmax, float* partial, float* dx, size_t n,
+                                   paif_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -3,10 +3,11 @@ MI355X-native counterparts of the reference's core/model_fusion_auto.py classes 
 path (SURVEY.md 8(a): F1-F8, G1, S1).  Same names, constructor signatures and state_dict keys;
 forward() bodies launch the hand-written gfx950 kernels of libpaif_hip.so.
 
-DRDB and Fusion_Network (:118-188, the hand-designed network) live in fusion_model/drdb.py and are exported from here.
+DRDB and Fusion_Network (:118-188, the hand-designed network) live in fusion_model/drdb.py, Fusion_Network2 (:227-260) in
+fusion_model/skff.py, and SKFF (:190-224, the same class as operations_m.py:399-433) in operations_m.py; all are exported from here.
 
-Not reproduced (out of scope, never constructed by either entry script): Fusion_Network2 / _auto / _Add / ...,
-SKFF, the GAN pieces, Network_MM_TARDAL/UMF/Base/Auto, the *_showfeatures variants.
+Not reproduced (out of scope, never constructed by either entry script): Fusion_Network_auto / _Add / _Average / _Max / _SPA (they need
+Cell_Chain at C = 64), the GAN pieces, Network_MM_TARDAL/UMF/Base/Auto, the other *_showfeatures variants.
 """
 import torch
 import torch.nn as nn
@@ -943,3 +944,4 @@ class Network_MM_SearchedFusion(nn.Module):
 
 # the hand-designed fusion network of :118-188 (imported last: fusion_model/drdb.py needs nothing of this module)
 from ..fusion_model.drdb import DRDB, Fusion_Network  # noqa: E402,F401
+from ..fusion_model.skff import SKFF, Fusion_Network2  # noqa: E402,F401  (SKFF is operations_m.SKFF: one class)

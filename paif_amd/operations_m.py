@@ -796,6 +796,80 @@ class SelfPath(_HipOp):
         return ops.conv2d([d_tok.view(B, H, W, C)], self._dgrad_w("c1", self.conv.weight), 3, 1, in_act=ops.IN_DPRELU, in_aux=t["r"], in_prelu=a)
 
 
+_SKFF_NO_WGRAD = "SKFF: parameter gradients (training the block) are not built"
+_SKFF_FREEZE = " -- freeze the parameters (requires_grad_(False)), or run under ops.no_param_grads() / torch.no_grad() for input gradients"
+
+
+class SKFF(nn.Module):
+    """operations_m.py:399-433 (the same class as core/model_fusion_auto.py:190-224): selective-kernel feature fusion.  A list of
+    `height` maps [B,64,H,W] -> [B,64,H,W]: per image and channel a softmax over the maps, computed from their pooled sum, weights them.
+    The reference's signature, module tree and state_dict keys (conv_du.0, conv_du.1, fcs.h).  Built: in_channels = 64, height 2 or 3,
+    any reduction >= 1, bias either way; fp32 device tensors; every input gets its gradient, parameters none (csrc/skff.hip: three
+    launches forward, three in reverse, between the NCHW <-> NHWC copies)."""
+
+    def __init__(self, in_channels, height=3, reduction=8, bias=False):
+        super().__init__()
+        if in_channels != 64:
+            raise NotImplementedError("SKFF: only in_channels = 64 (the width Fusion_Network2 uses) is built, got in_channels = %r" % (in_channels,))
+        if height not in (2, 3):
+            raise NotImplementedError("SKFF: only height = 2 or 3 is built, got height = %r" % (height,))
+        if not reduction >= 1:
+            raise NotImplementedError("SKFF: only reduction >= 1 is built (d = max(int(64 / reduction), 4) <= 64), got reduction = %r" % (reduction,))
+        self.height = height
+        d = max(int(in_channels / reduction), 4)
+        self.avg_pool = nn.AdaptiveAvgPool2d(1)
+        self.conv_du = nn.Sequential(nn.Conv2d(in_channels, d, 1, padding=0, bias=bias), nn.PReLU())
+        self.fcs = nn.ModuleList([])
+        for i in range(self.height):
+            self.fcs.append(nn.Conv2d(d, in_channels, kernel_size=1, stride=1, bias=bias))
+        self.softmax = nn.Softmax(dim=1)
+        self._packs = _PackCache()
+
+    def _pack(self):
+        du, act = self.conv_du[0], self.conv_du[1]
+        params = [p for p in self.parameters()]
+        return self._packs.get("skff", params, lambda: ops.skff_pack(du.weight, du.bias, act.weight, [(fc.weight, fc.bias) for fc in self.fcs]))
+
+    def _check(self, inp_feats):
+        if not isinstance(inp_feats, (list, tuple)) or len(inp_feats) != self.height:
+            raise ValueError("SKFF: a list of %d maps is expected (height = %d), got %s"
+                             % (self.height, self.height, len(inp_feats) if isinstance(inp_feats, (list, tuple)) else type(inp_feats).__name__))
+        for x in inp_feats:
+            if not x.is_cuda:
+                raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got a %s tensor -- there is no CPU path" % x.device)
+        for x in inp_feats:
+            if x.dtype != torch.float32:
+                raise TypeError("SKFF: fp32 maps are expected, got %s" % x.dtype)
+        x0 = inp_feats[0]
+        if x0.dim() != 4 or x0.shape[1] != 64 or any(x.shape != x0.shape for x in inp_feats):
+            raise ValueError("SKFF: %d [B,64,H,W] maps of one shape are expected, got %s" % (self.height, [tuple(x.shape) for x in inp_feats]))
+
+    def forward(self, inp_feats):
+        if ops.want_param_grads(self):
+            raise NotImplementedError(_SKFF_NO_WGRAD + _SKFF_FREEZE)
+        self._check(inp_feats)
+        if torch.is_grad_enabled() and any(x.requires_grad for x in inp_feats):
+            return _SKFFFn.apply(self, grad_anchor(inp_feats[0].device), *inp_feats)
+        with torch.no_grad():
+            return ops.skff_forward(list(inp_feats), self._pack())[1]
+
+
+class _SKFFFn(torch.autograd.Function):
+    """Autograd node of an SKFF alone: hand-written reverse pass, every input's gradient."""
+
+    @staticmethod
+    def forward(ctx, module, anchor, *xs):
+        tape, out = ops.skff_forward([x.detach() for x in xs], module._pack())
+        ctx.tape, ctx.module = tape, module
+        return out
+
+    @staticmethod
+    def backward(ctx, d_out):
+        grads = ops.skff_backward(ctx.tape, d_out.contiguous(), ctx.module._pack(), want=ctx.needs_input_grad[2:])
+        ctx.tape = None
+        return (None, None) + tuple(grads)
+
+
 # operations_m.py:9-18
 OPS = {
     'Denseblocks': lambda C, kernel, dialtion, affine: ResidualDenseBlock(C, kernel, dialtion),

@@ -3154,3 +3154,200 @@ def drdb_block_backward(maps, d_out, pack):
     d_slab = torch.empty_like(maps["slab"])
     _drdb_block_bwd(_p(pack.weights), 0, maps["slab"], maps["r6"], g, d_slab, B, H, W)
     return d_slab[..., 0:64].permute(0, 3, 1, 2).contiguous()
+
+
+# ---------------------------------------------------------------------------------------------
+# SKFF and Fusion_Network2 (csrc/skff.hip; operations_m.SKFF and fusion_model/skff.py are the modules)
+# ---------------------------------------------------------------------------------------------
+class SkffPack:
+    """The gate's parameters of one SKFF in the kernels' order, its shape and its PReLU slope as a Python float."""
+
+    __slots__ = ("weights", "height", "d", "slope")
+
+    def __init__(self, weights, height, d, slope):
+        self.weights, self.height, self.d, self.slope = weights, int(height), int(d), float(slope)
+
+
+def skff_pack(du_weight, du_bias, slope, fcs):
+    """du_weight [d,64,1,1], du_bias [d] or None: conv_du.0; slope: conv_du.1's PReLU weight (a one-element tensor or a float), read to the
+    host HERE, once per pack (any sign: the reverse pass reads the branch off the taped z); fcs: (weight [64,d,1,1], bias [64] or None) per
+    input -> SkffPack."""
+    n, d = len(fcs), du_weight.shape[0]
+    if n not in (2, 3) or du_weight.shape[1] != 64 or not 1 <= d <= 64:
+        raise ValueError("skff_pack: 64 channels, 2 or 3 inputs and d <= 64 are built, got %d channels, %d inputs, d = %d" % (du_weight.shape[1], n, d))
+    host = float(slope.detach().reshape(-1)[0]) if torch.is_tensor(slope) else float(slope)
+    dev = du_weight.device
+
+    def flat(t, count):
+        return torch.zeros(count, device=dev, dtype=torch.float32) if t is None else t.detach().to(torch.float32).reshape(-1)
+
+    parts = [flat(du_weight, d * 64), flat(du_bias, d)] + [flat(w, 64 * d) for w, _ in fcs] + [flat(b, 64) for _, b in fcs]
+    pack = torch.cat(parts).contiguous()
+    assert pack.numel() == lib().paif_skff_pack_floats(n, d)
+    return SkffPack(pack, n, d, host)
+
+
+def _skff_inputs(xs):
+    """Channel-last views [B,H,W,>=64] whose first 64 channels are the inputs -> the six (pointer, pixel stride) arguments."""
+    args = []
+    for x in xs:
+        args += [_p(x), x.shape[-1]]
+    return args + [None, 0] * (3 - len(xs))
+
+
+def skff_forward_nhwc(xs, pack, out=None):
+    """xs: the inputs as dense channel-last maps (the first 64 channels of each are used); out: the dense map whose channels [0, 64) receive
+    V (default: a new [B,H,W,64]) -> (tape, out).  tape: a [B,n,64], z [B,d].  Three launches."""
+    B, H, W, _ = xs[0].shape
+    dev = xs[0].device
+    L = lib()
+    if out is None:
+        out = torch.empty((B, H, W, 64), device=dev, dtype=torch.float32)
+    partial = torch.empty(B * L.paif_skff_blocks(H, W) * 64, device=dev, dtype=torch.float32)
+    a = torch.empty((B, pack.height, 64), device=dev, dtype=torch.float32)
+    z = torch.empty((B, pack.d), device=dev, dtype=torch.float32)
+    _lib.check(L.paif_skff_fwd(*_skff_inputs(xs), pack.height, pack.d, _p(pack.weights), pack.slope, _p(partial), _p(a), _p(z), _p(out),
+                               out.shape[-1], 0, B, H, W, _stream()), "skff_fwd")
+    return dict(a=a, z=z), out
+
+
+def skff_backward_nhwc(xs, tape, d_v, pack, want=None):
+    """Reverse of skff_forward_nhwc.  d_v: a dense channel-last map whose first 64 channels are dV; want: per input whether its gradient
+    is built (default: all) -> the list of d_x_h [B,H,W,64] (None where not wanted).  Three launches."""
+    B, H, W, _ = xs[0].shape
+    dev = xs[0].device
+    L = lib()
+    want = [True] * len(xs) if want is None else list(want)
+    partial = torch.empty(B * L.paif_skff_blocks(H, W) * 64 * pack.height, device=dev, dtype=torch.float32)
+    d_s = torch.empty((B, 64), device=dev, dtype=torch.float32)
+    d_xs = [torch.empty((B, H, W, 64), device=dev, dtype=torch.float32) if w else None for w in want]
+    _lib.check(L.paif_skff_bwd(*_skff_inputs(xs), pack.height, pack.d, _p(pack.weights), pack.slope, _p(tape["a"]), _p(tape["z"]), _p(d_v),
+                               d_v.shape[-1], _p(partial), _p(d_s), *[_p(g) for g in d_xs + [None] * (3 - len(xs))], B, H, W, _stream()),
+               "skff_bwd")
+    return d_xs
+
+
+def skff_forward(xs, pack):
+    """SKFF alone: n [B,64,H,W] fp32 NCHW maps -> (tape, V [B,64,H,W]).  Three launches between the layout copies."""
+    maps = [x.permute(0, 2, 3, 1).contiguous() for x in xs]
+    tape, out = skff_forward_nhwc(maps, pack)
+    tape["x"] = maps
+    return tape, out.permute(0, 3, 1, 2).contiguous()
+
+
+def skff_backward(tape, d_out, pack, want=None):
+    """Reverse of skff_forward: dV [B,64,H,W] -> the list of d_x_h [B,64,H,W] (None where not wanted).  Three launches between the layout
+    copies."""
+    d_xs = skff_backward_nhwc(tape["x"], tape, d_out.permute(0, 2, 3, 1).contiguous(), pack, want)
+    return [None if g is None else g.permute(0, 3, 1, 2).contiguous() for g in d_xs]
+
+
+def plane_minmax(x):
+    """x [B,1,H,W] -> ((x - min x) / (max x - min x) over the whole tensor, NO clamp; the 2 floats (min, max) the reverse pass needs).
+    Two launches."""
+    x = x.contiguous()
+    L = lib()
+    n = x.numel()
+    partial = torch.empty(2 * L.paif_plane_minmax_nc_blocks(n), device=x.device, dtype=torch.float32)
+    out, mm = torch.empty_like(x), torch.empty(2, device=x.device, dtype=torch.float32)
+    _lib.check(L.paif_plane_minmax_nc_fwd(_p(x), _p(out), _p(partial), _p(mm), n, _stream()), "plane_minmax")
+    return out, mm
+
+
+def plane_minmax_bwd(dout, x, mm):
+    """Reverse of plane_minmax; the gradient of an extremum is spread evenly over the elements that attain it.  Two launches."""
+    x = x.contiguous()
+    L = lib()
+    n = x.numel()
+    partial = torch.empty(4 * L.paif_plane_minmax_nc_blocks(n), device=x.device, dtype=torch.float32)
+    dx = torch.empty_like(x)
+    _lib.check(L.paif_plane_minmax_nc_bwd_input(_p(dout.contiguous()), _p(x), _p(mm), _p(partial), _p(dx), n, _stream()), "plane_minmax_bwd")
+    return dx
+
+
+class Fn2Pack:
+    """The packed weights of Fusion_Network2: the DrdbPack of conv1, DRDB1 and DRDB2 (with the one PReLU slope), the pack of conv3, conv4
+    and conv2, and the two gates' SkffPack."""
+
+    __slots__ = ("drdb", "weights", "skff", "skff2")
+
+    def __init__(self, drdb, weights, skff, skff2):
+        self.drdb, self.weights, self.skff, self.skff2 = drdb, weights, skff, skff2
+
+
+def fn2_pack(convs, slope, skff, skff2):
+    """convs: (weight, bias) of the sixteen Conv2d outside the gates in paif_amd.synthetic.FN2_CONVS order (conv1, DRDB1.*, DRDB2.*, conv2,
+    conv3, conv4); slope: relu.weight, read to the host HERE, once per pack, refused when negative (the reverse pass reads the branch off
+    the taped output); skff, skff2: the gates' SkffPack -> Fn2Pack."""
+    if len(convs) != 16:
+        raise ValueError("fn2_pack: sixteen convs are expected, got %d" % len(convs))
+    host = float(slope.detach().reshape(-1)[0]) if torch.is_tensor(slope) else float(slope)
+    if not host >= 0.0:
+        raise ValueError("Fusion_Network2: the PReLU slope is %g; the reverse pass reads the branch off the taped output, which is right for "
+                         "slopes >= 0 only" % host)
+    drdb = drdb_pack(list(convs[:13]) + [None, None], host)
+    pack = torch.zeros(lib().paif_fn2_pack_floats(), device=convs[0][0].device, dtype=torch.float32)
+    for conv, k in ((2, 13), (0, 14), (1, 15)):
+        w, b = convs[k]
+        _lib.check(lib().paif_fn2_pack_conv(_p(w.detach().contiguous()), _p(b.detach().contiguous()), conv, _p(pack), _stream()), "fn2_pack_conv")
+    return Fn2Pack(drdb, pack, skff, skff2)
+
+
+def fn2_forward(ir, vis, out1, out2, pack):
+    """Two [B,1,H,W] planes (channel 0 of the reference's ir and vis), out1 [B,64,H,W], out2 [B,128,H,W] -> (maps, fused [B,1,H,W]).  maps:
+    slab [B,H,W,224] and r6 [B,H,W,64] per DRDB, f1, c3, f2, c4, v2 [B,H,W,64], the gates' tapes g1, g2 (a, z), f [B,1,H,W] (conv2's PReLU
+    output before the normalisation) and minmax, all fp32.  24 launches between the guidance maps' layout copies: conv1 1, DRDB1 6, conv3
+    1, skff 3, DRDB2 6, conv4 1, skff2 3, conv2 1, the normalisation 2."""
+    B, _, H, W = ir.shape
+    L = lib()
+    dev = ir.device
+    (_, p_ir, sb_ir), (_, p_vis, sb_vis) = keep = (_plane(ir), _plane(vis))
+    g1n, g2n = out1.permute(0, 2, 3, 1).contiguous(), out2.permute(0, 2, 3, 1).contiguous()
+
+    def new(c):
+        return torch.empty((B, H, W, c), device=dev, dtype=torch.float32)
+
+    wp, sl, fp = _p(pack.drdb.weights), pack.drdb.slope, _p(pack.weights)
+    slab, r6 = [new(224), new(224)], [new(64), new(64)]
+    f1, c3, f2, c4 = new(64), new(64), new(64), new(64)
+    f = torch.empty((B, 1, H, W), device=dev, dtype=torch.float32)
+    _lib.check(L.paif_drdb_stem_fwd(p_ir, sb_ir, p_vis, sb_vis, wp, sl, _p(slab[0]), B, H, W, _stream()), "drdb_stem_fwd")
+    _drdb_block_fwd(wp, 0, slab[0], f1, r6[0], B, H, W)
+    _lib.check(L.paif_fn2_guide_fwd(fp, 0, _p(g1n), _p(c3), B, H, W, _stream()), "fn2_guide_fwd")
+    g1, _ = skff_forward_nhwc([f1, c3], pack.skff, out=slab[1])
+    _drdb_block_fwd(wp, 1, slab[1], f2, r6[1], B, H, W)
+    _lib.check(L.paif_fn2_guide_fwd(fp, 1, _p(g2n), _p(c4), B, H, W, _stream()), "fn2_guide_fwd")
+    g2, v2 = skff_forward_nhwc([f2, c4], pack.skff2)
+    _lib.check(L.paif_fn2_head_fwd(fp, sl, _p(v2), _p(f), B, H, W, _stream()), "fn2_head_fwd")
+    fused, mm = plane_minmax(f)
+    del keep
+    return dict(slab=slab, r6=r6, f1=f1, c3=c3, f2=f2, c4=c4, v2=v2, g1=g1, g2=g2, f=f, minmax=mm), fused
+
+
+def fn2_backward(maps, d_fused, pack, want_guides=True):
+    """Reverse of fn2_forward (input gradients) from the taped maps -> (d_ir, d_vis [B,1,H,W], d_out1 [B,64,H,W], d_out2 [B,128,H,W]).
+    want_guides False: d_out1 and d_out2 are None, the gates skip the gradients of c3 and c4 and the two transposed 1x1 launches are not
+    made.  24 launches without the guidance gradients (the normalisation 2, conv2 1, skff2 3, DRDB2 7, skff 3, DRDB1 7, conv1 1), 26 with
+    them plus the two layout copies; nothing is recomputed and nothing needs a memset."""
+    B, _, H, W = maps["f"].shape
+    L = lib()
+    wp, sl, fp = _p(pack.drdb.weights), pack.drdb.slope, _p(pack.weights)
+    want = [True, bool(want_guides)]
+    d_f = plane_minmax_bwd(d_fused, maps["f"], maps["minmax"])
+    d_v2 = torch.empty_like(maps["v2"])
+    d_slab = [torch.empty_like(maps["slab"][0]), torch.empty_like(maps["slab"][1])]
+    _lib.check(L.paif_fn2_head_bwd(fp, sl, _p(maps["f"]), _p(d_f), _p(d_v2), B, H, W, _stream()), "fn2_head_bwd")
+    d_f2, d_c4 = skff_backward_nhwc([maps["f2"], maps["c4"]], maps["g2"], d_v2, pack.skff2, want)
+    _drdb_block_bwd(wp, 1, maps["slab"][1], maps["r6"][1], d_f2, d_slab[1], B, H, W)
+    d_f1, d_c3 = skff_backward_nhwc([maps["f1"], maps["c3"]], maps["g1"], d_slab[1], pack.skff, want)
+    _drdb_block_bwd(wp, 0, maps["slab"][0], maps["r6"][0], d_f1, d_slab[0], B, H, W)
+    d_ir, d_vis = torch.empty_like(maps["f"]), torch.empty_like(maps["f"])
+    _lib.check(L.paif_drdb_stem_bwd(wp, sl, _p(maps["slab"][0]), _p(d_slab[0]), _p(d_ir), _p(d_vis), B, H, W, _stream()), "drdb_stem_bwd")
+    d_out1 = d_out2 = None
+    if want_guides:
+        d1 = torch.empty((B, H, W, 64), device=d_ir.device, dtype=torch.float32)
+        d2 = torch.empty((B, H, W, 128), device=d_ir.device, dtype=torch.float32)
+        _lib.check(L.paif_fn2_guide_bwd(fp, 0, _p(d_c3), _p(d1), B, H, W, _stream()), "fn2_guide_bwd")
+        _lib.check(L.paif_fn2_guide_bwd(fp, 1, _p(d_c4), _p(d2), B, H, W, _stream()), "fn2_guide_bwd")
+        d_out1, d_out2 = d1.permute(0, 3, 1, 2).contiguous(), d2.permute(0, 3, 1, 2).contiguous()
+    return d_ir, d_vis, d_out1, d_out2

@@ -275,6 +275,65 @@ def drdb_state_dict(scales, shift=0.0, last_scale=1.0):
     return sd
 
 
+# Fusion_Network2 (reference core/model_fusion_auto.py:227-260).  FN2_CONVS: its sixteen Conv2d outside the gates, as DRDB_CONVS (the order
+# of ops.fn2_pack); FN2_GATE_CONVS: per gate conv_du.0 and the two fcs (1x1, no bias).  FN2_SCALED: the 22 convs a calibration rescales.
+FN2_CONVS = DRDB_CONVS[:13] + (("conv2", 1, 64, 3), ("conv3", 64, 64, 1), ("conv4", 64, 128, 1))
+SKFF_D = 8       # max(int(64 / 8), 4)
+
+
+def skff_convs(prefix, height=2, d=SKFF_D):
+    return ((prefix + "conv_du.0", d, 64, 1),) + tuple(("%sfcs.%d" % (prefix, h), 64, d, 1) for h in range(height))
+
+
+FN2_GATE_CONVS = skff_convs("skff.") + skff_convs("skff2.")
+FN2_SCALED = FN2_CONVS + FN2_GATE_CONVS
+FN2_PREFIX = "hand2/"
+
+
+def skff_state_dict(scales, height=2, reduction=8, bias=False, prefix="", formula_prefix=FN2_PREFIX):
+    """key -> numpy array of one SKFF(64, height, reduction, bias) in the reference's state_dict order: formula tensors, conv_du.0 times
+    scales[0], fcs.h times scales[1 + h] (weight and bias alike); conv_du.1.weight (the PReLU slope) is the formula value."""
+    d = max(int(64 / reduction), 4)
+    sd = {}
+
+    def conv(name, cout, cin, s):
+        sd[prefix + name + ".weight"] = formula_tensor(formula_prefix + prefix + name + ".weight", (cout, cin, 1, 1)) * np.float32(s)
+        if bias:
+            sd[prefix + name + ".bias"] = formula_tensor(formula_prefix + prefix + name + ".bias", (cout,)) * np.float32(s)
+
+    conv("conv_du.0", d, 64, scales[0])
+    sd[prefix + "conv_du.1.weight"] = formula_tensor(formula_prefix + prefix + "conv_du.1.weight", (1,))
+    for h in range(height):
+        conv("fcs.%d" % h, 64, d, scales[1 + h])
+    return sd
+
+
+def fn2_state_dict(scales, shift=0.0, last_scale=1.0):
+    """key -> numpy array (41 entries, the reference's state_dict order): formula_tensor(FN2_PREFIX + key) times the conv's scale (weight
+    and bias alike; `scales` in FN2_SCALED order); conv2's weight and bias are further multiplied by `last_scale` and `shift` is then added
+    to its bias; relu.weight and the gates' PReLU slopes are the formula values, in [0.1, 0.3).  The tool and the tests rebuild the fixture
+    weights with this one expression."""
+    scales = np.asarray(scales, dtype=np.float32)
+    assert scales.shape == (len(FN2_SCALED),)
+    by = {name: s for (name, _, _, _), s in zip(FN2_SCALED, scales)}
+
+    def conv(sd, name, cout, cin, k):
+        sd[name + ".weight"] = formula_tensor(FN2_PREFIX + name + ".weight", (cout, cin, k, k)) * by[name]
+        sd[name + ".bias"] = formula_tensor(FN2_PREFIX + name + ".bias", (cout,)) * by[name]
+
+    sd = {}
+    for name, cout, cin, k in FN2_CONVS[:14]:
+        conv(sd, name, cout, cin, k)
+    sd["conv2.weight"] = sd["conv2.weight"] * np.float32(last_scale)
+    sd["conv2.bias"] = sd["conv2.bias"] * np.float32(last_scale) + np.float32(shift)
+    sd["relu.weight"] = formula_tensor(FN2_PREFIX + "relu.weight", (1,))
+    for g in ("skff.", "skff2."):
+        sd.update(skff_state_dict([by[g + "conv_du.0"], by[g + "fcs.0"], by[g + "fcs.1"]], prefix=g))
+    for name, cout, cin, k in FN2_CONVS[14:]:
+        conv(sd, name, cout, cin, k)
+    return sd
+
+
 # The BFFusion baseline (reference fusion_model/BFFusion.py, class BFFR).  BFFUSION_LAYERS: its 97 convs and linears in state_dict order,
 # as (state_dict prefix of `.weight`, weight shape, has a bias, kind, BatchNorm prefix or None).  kind: "stem" (1 x 1, no activation),
 # "dense" (LeakyReLU 0.2 / 0.1), "fconv" (BatchNorm + ReLU: the 32 BatchNorms that ARE applied), "q", "k", "v", "proj" (the attention's
