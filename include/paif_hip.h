@@ -582,6 +582,32 @@ int paif_attack_loss_bwd(const float* logits, const long long* label, const floa
                          float w_false, float upstream, int B, int IH, int IW, int C, int OH, int OW, int ignore_index, int CP,
                          paif_stream_t stream);
 
+/* The segmentation criteria of the training path (core/loss.py:342-383) on bilinearly upsampled logits (F.interpolate
+ * align_corners=False), value and gradient w.r.t. the full-resolution logits.  logits NHWC [B,IH,IW,C], C <= 32; label int64
+ * [B,OH,OW]; n = B*OH*OW < 2^31; l_i = per-pixel cross entropy, 0 on ignored pixels (which still count as elements).
+ *   kind 0  NormalLoss        sum l_i / n
+ *   kind 1  SoftmaxFocalLoss  sum_valid -(1-p)^gamma log p / #valid        param = gamma >= 0
+ *   kind 2  OhemCELoss        cnt = #{l_i > T} >= n_min: mean{l_i > T} (mode A); else the mean of the n_min largest (mode B)
+ *                             param = T = -log(thresh) >= 0, 1 <= n_min <= n
+ * fwd: lplane, lseplane = [B,OH,OW] floats (l_i or the focal term, and logsumexp; read by bwd); workspace =
+ *      paif_seg_criterion_workspace_words(B,OH,OW) 4-byte words of scratch; coef[8] (device) = {value, mode (0 | 1 = A | 2 = B),
+ *      threshold (T or the n_min-th largest l; -1 for kinds 0 and 1), weight where l > threshold, weight where l == threshold,
+ *      #valid, nbad, #{l > threshold}}; nbad = labels outside [0, C) that are not ignore_index: dropped like ignored pixels, never
+ *      used as an index.  The n_min-th largest value is selected exactly on the device (radix select on the bit pattern, integer
+ *      atomics only); nothing returns to the host.
+ * bwd: dfull [B,OH,OW,CP] = upstream[0] * d value / d o (CP >= C, CP % 4 == 0, zero padded); reads lplane, lseplane and coef of fwd
+ *      and the upstream gradient from the device; follow with paif_resize_bilinear_adjoint_fwd to get dlogits.  In mode B the
+ *      pixels that tie at the threshold share the remaining weight equally.
+ * Deterministic (fixed-order reductions, no float atomics).  paif_seg_criterion_blocks = the launches' grid (0 for an empty shape). */
+int paif_seg_criterion_blocks(int B, int OH, int OW);
+size_t paif_seg_criterion_workspace_words(int B, int OH, int OW);
+int paif_seg_criterion_fwd(const float* logits, const long long* label, float* lplane, float* lseplane, void* workspace,
+                           float* coef, int kind, float param, int n_min, int B, int IH, int IW, int C, int OH, int OW,
+                           int ignore_index, paif_stream_t stream);
+int paif_seg_criterion_bwd(const float* logits, const long long* label, const float* lplane, const float* lseplane,
+                           const float* coef, const float* upstream, float* dfull, int kind, float gamma, int B, int IH, int IW,
+                           int C, int OH, int OW, int ignore_index, int CP, paif_stream_t stream);
+
 /* ---- fusion-network dgrad helpers (dense-conv dgrads go through paif_conv2d_fwd with these weights and the
  * in_act 3/4/5, epi_dact hooks of paif_conv_desc) ---- */
 /* forward w [Co,Ctot,k,k] -> dgrad weight w.r.t. source channels [coff,coff+cs): wt [cs,Co,k,k],

@@ -13,7 +13,19 @@ and `mask` is read in place.  `Fusionloss_grad3` (:504-515) is MSE + 1.1 * (1 - 
 differentiable w.r.t. the generated image only: `ir`, `vis` or `mask` requiring grad under recording autograd raises NotImplementedError.
 A class that reads its image arguments says so with `reads_images = True`; the composite models then refuse `ir` / `vis` that require
 grad in their `_loss*` methods instead of dropping the criterion's direct image term.  Not built: `new_loss_sobel`,
-`Total_fusion_loss`, `Total_fusion_loss2`, `IQALoss` / `Entropy`, `Fusionloss_grad`, and the segmentation / FCOS criteria."""
+`Total_fusion_loss`, `Total_fusion_loss2`, `IQALoss` / `Entropy`, `Fusionloss_grad`, and the FCOS criteria.
+
+The segmentation criteria of core/loss.py:342-383 -- `OhemCELoss`, `SoftmaxFocalLoss`, `NormalLoss` -- run on csrc/seg_criteria.hip
+(ops.seg_criterion): `forward(logits, labels)` is the reference's call on full-resolution logits, `from_seg_map(seg_map, labels)` takes
+the head's low-resolution map and folds F.interpolate(bilinear, align_corners=False) into the same kernels, which is the route the
+composite models take (`takes_seg_map = True`).  Value and gradient stay on the device: OHEM's n_min-th largest loss comes from an exact
+radix select, not from a sort.  Limits: C <= 32 classes (above that `forward` and the composite models compute the criterion with torch
+ops, `from_seg_map` and ops.seg_criterion raise NotImplementedError); gradients w.r.t. the logits only; no class weights or label
+smoothing.  A label outside [0, C) that is not `ignore_lb` is dropped like an ignored pixel (torch raises).
+Differences from torch, both in the gradient only: OHEM pixels that tie at the n_min-th largest loss share the remaining weight equally
+(torch's sort hands it to an unspecified subset of them; the value is the same, and ties at 0 -- ignored pixels -- carry no gradient
+either way); the focal gradient is 0 where 1 - p is exactly 0 (torch gives NaN there for 0 < gamma < 1).  `OhemCELoss` refuses `n_min`
+outside [1, number of pixels] with a ValueError at the call (the reference raises IndexError above and is silently wrong at 0)."""
 import torch
 import torch.nn as nn
 
@@ -179,3 +191,92 @@ class Total_fusion_loss3(nn.Module):
 
     def forward(self, image_ir, image_vis, mask, generate_img):
         return ops.sobel_criterion(generate_img, image_ir, image_vis, None, [(_MAX, 3.0, 0.0, 0.0)], (_MAX, 24.0, 0.0, 0.0))
+
+
+class _SegCriterion(nn.Module):
+    """One fused route for the three segmentation criteria: `from_seg_map` upsamples inside the kernels, `forward` is the identity-scale
+    case of the same kernels.  `takes_seg_map` is what `_CompositeBase._seg_term` recognises.  No parameters, no buffers."""
+
+    takes_seg_map = True
+    seg_kind = None
+
+    def _seg_params(self):
+        return {}
+
+    def from_seg_map(self, seg_map, labels):
+        """criterion(F.interpolate(seg_map, size=labels.shape[1:], mode='bilinear', align_corners=False), labels), seg_map [B,C,h,w]."""
+        return ops.seg_criterion(seg_map, labels.type(torch.long), self.seg_kind, ignore_index=self.ignore_lb, **self._seg_params())
+
+    def forward(self, logits, labels):
+        if logits.dim() != 4 or labels.dim() != 3 or tuple(logits.shape[2:]) != tuple(labels.shape[1:]):
+            raise ValueError("expected logits [B,C,H,W] and labels [B,H,W] of one size, got %s and %s (from_seg_map takes a low-resolution "
+                             "map)" % (tuple(logits.shape), tuple(labels.shape)))
+        if logits.shape[1] > ops.SEG_MAXC:
+            # more classes than the kernels take: the torch route, where the composite models send such a criterion (`_seg_term`)
+            return self._torch_forward(logits, labels.type(torch.long))
+        return self.from_seg_map(logits, labels)
+
+    def _pixel_ce(self, logits, labels):
+        return nn.functional.cross_entropy(logits, labels, ignore_index=self.ignore_lb, reduction="none")
+
+
+class OhemCELoss(_SegCriterion):
+    """core/loss.py:342-358: with l the per-pixel cross entropy sorted in descending order, the mean of {l > T} if l[n_min - 1] > T, else
+    the mean of the n_min largest; T = -log(thresh) in float32.  `thresh` holds T as a plain float (the reference keeps a 0-d tensor)."""
+
+    seg_kind = "ohem"
+
+    def __init__(self, thresh, n_min, ignore_lb=255, *args, **kwargs):
+        super().__init__()
+        if not 0.0 < thresh <= 1.0:
+            raise ValueError("OhemCELoss: thresh must lie in (0, 1], got %r" % (thresh,))
+        self.thresh = float(-torch.log(torch.tensor(thresh, dtype=torch.float)))
+        self.n_min = n_min
+        self.ignore_lb = ignore_lb
+
+    @property
+    def T(self):
+        return self.thresh
+
+    def _seg_params(self):
+        return dict(T=self.thresh, n_min=self.n_min)
+
+    def _torch_forward(self, logits, labels):
+        l = self._pixel_ce(logits, labels).flatten()
+        if not 1 <= self.n_min <= l.numel():
+            raise ValueError("OhemCELoss: n_min = %r outside [1, %d] (the number of pixels)" % (self.n_min, l.numel()))
+        above = l > self.thresh
+        return l[above].mean() if int(above.sum()) >= self.n_min else torch.topk(l, self.n_min).values.mean()
+
+
+class SoftmaxFocalLoss(_SegCriterion):
+    """core/loss.py:361-373: NLLLoss(ignore_index)((1 - softmax)^gamma * log_softmax, labels), the mean over the valid pixels."""
+
+    seg_kind = "focal"
+
+    def __init__(self, gamma, ignore_lb=255, *args, **kwargs):
+        super().__init__()
+        if not gamma >= 0:
+            raise ValueError("SoftmaxFocalLoss: built for gamma >= 0, got %r" % (gamma,))
+        self.gamma = gamma
+        self.ignore_lb = ignore_lb
+
+    def _seg_params(self):
+        return dict(gamma=float(self.gamma))
+
+    def _torch_forward(self, logits, labels):
+        logp = torch.log_softmax(logits, dim=1)
+        return nn.functional.nll_loss(torch.pow(1.0 - torch.exp(logp), self.gamma) * logp, labels, ignore_index=self.ignore_lb)
+
+
+class NormalLoss(_SegCriterion):
+    """core/loss.py:375-383: the mean of CrossEntropyLoss(ignore_index, reduction='none') over ALL pixels, the ignored ones included."""
+
+    seg_kind = "normal"
+
+    def __init__(self, ignore_lb=255, *args, **kwargs):
+        super().__init__()
+        self.ignore_lb = ignore_lb
+
+    def _torch_forward(self, logits, labels):
+        return self._pixel_ce(logits, labels).mean()

@@ -776,6 +776,9 @@ class _CompositeBase(nn.Module):
         if isinstance(sl, nn.CrossEntropyLoss) and sl.reduction == "mean" and sl.weight is None and sl.label_smoothing == 0.0:
             # fused bilinear upsample + cross entropy, forward and gradient (HIP; ops.UpsampleCE is the autograd node)
             return ops.upsample_ce(seg_map, labels, ignore_index=sl.ignore_index)
+        if getattr(sl, "takes_seg_map", False) and seg_map.shape[1] <= ops.SEG_MAXC:
+            # core/loss.py's OhemCELoss / SoftmaxFocalLoss / NormalLoss: the upsample folded into the criterion's HIP kernels
+            return sl.from_seg_map(seg_map, labels)
         # any other user criterion: the reference's own two calls on torch ops above the HIP model
         import torch.nn.functional as F
         return sl(F.interpolate(seg_map, size=labels.shape[1:], mode='bilinear', align_corners=False), labels)

@@ -2,6 +2,7 @@
 // (attack/attack.py:443-501: loss.backward() through WeTr).  Weight gradients are NOT produced: the
 // attack only consumes d(loss)/d(input) (the reference additionally accumulates unused .grad on every
 // parameter).  GEMM dgrads reuse gemm_mfma.hip with transposed weights.
+#include "bilinear_src.h"
 #include "paif_common.h"
 
 namespace {
@@ -262,13 +263,7 @@ __global__ __launch_bounds__(256) void col2im_kernel(const float* __restrict__ d
 // ---------------------------------------------------------------------------------------------
 // adjoint of paif_resize_bilinear_into_fwd (gather form): dx[b,iy,ix,c] = sum_o w(o -> i) * dout[b,o,coff+c]
 // ---------------------------------------------------------------------------------------------
-__device__ __forceinline__ void src_index(float scale, int o, int isz, int& i0, int& i1, float& l1) {
-  float f = scale * ((float)o + 0.5f) - 0.5f;
-  f = f < 0.f ? 0.f : f;
-  i0 = (int)f;
-  i1 = i0 + (i0 < isz - 1 ? 1 : 0);
-  l1 = f - (float)i0;
-}
+using paif::src_index;   // bilinear_src.h: shared with seg_criteria.hip
 
 __global__ __launch_bounds__(256) void resize_adjoint_kernel(const float* __restrict__ dout, float* __restrict__ dx, int B, int IH,
                                                              int IW, int C, int OH, int OW, int ldo, int coff) {

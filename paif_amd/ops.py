@@ -1997,6 +1997,103 @@ def upsample_ce(seg_map, label, ignore_index=255):
     return upsample_ce_fwd(to_nhwc(seg_map.detach()), label, ignore_index)[0]
 
 
+# ---- segmentation criteria (core/loss.py:342-383) on csrc/seg_criteria.hip ----
+SEG_NORMAL, SEG_FOCAL, SEG_OHEM = 0, 1, 2
+SEG_KINDS = {"normal": SEG_NORMAL, "focal": SEG_FOCAL, "ohem": SEG_OHEM}
+SEG_MAXC = 32        # the kernels' channel limit (the CE_MAXC of upsample_ce)
+
+
+def _seg_criterion_args(logits, label, kind, gamma, T, n_min):
+    """Shape and parameter checks of seg_criterion_fwd, on the host and before any launch -> (kind code, param, n_min)."""
+    if kind not in SEG_KINDS:
+        raise ValueError("seg_criterion: kind %r (one of %s)" % (kind, sorted(SEG_KINDS)))
+    if logits.dim() != 4 or label.dim() != 3 or label.shape[0] != logits.shape[0] or logits.numel() == 0 or label.numel() == 0:
+        raise ValueError("seg_criterion: expected logits [B,IH,IW,C] and labels [B,OH,OW], got %s and %s"
+                         % (tuple(logits.shape), tuple(label.shape)))
+    if logits.shape[-1] > SEG_MAXC:
+        raise NotImplementedError("seg_criterion: built for C <= %d classes, got %d" % (SEG_MAXC, logits.shape[-1]))
+    if logits.dtype != torch.float32 or label.dtype != torch.int64:
+        raise TypeError("seg_criterion: expected float32 logits and int64 labels, got %s and %s" % (logits.dtype, label.dtype))
+    code, param, k = SEG_KINDS[kind], 0.0, 0
+    if code == SEG_FOCAL:
+        if not gamma >= 0:
+            raise ValueError("seg_criterion: focal gamma must be >= 0, got %r" % (gamma,))
+        param = float(gamma)
+    elif code == SEG_OHEM:
+        n = label.numel()
+        if int(n_min) != n_min or not 1 <= n_min <= n:
+            raise ValueError("seg_criterion: OHEM n_min = %r outside [1, %d] (the number of pixels)" % (n_min, n))
+        if not T >= 0:
+            raise ValueError("seg_criterion: OHEM T = -log(thresh) must be >= 0, got %r" % (T,))
+        param, k = float(T), int(n_min)
+    if not (logits.is_cuda and label.is_cuda):      # last, so that every refusal above is the same with and without a GPU
+        raise RuntimeError("paif_amd ops need CUDA(HIP) tensors; got %s (logits) and %s (labels) -- there is no CPU path"
+                           % (logits.device, label.device))
+    return code, param, k
+
+
+def seg_criterion_fwd(logits, label, kind, gamma=0.0, T=0.0, n_min=0, ignore_index=255):
+    """logits NHWC [B,IH,IW,C], label int64 [B,OH,OW] -> (coef [8], l plane, lse plane): paif_seg_criterion_fwd.  coef = (value, mode,
+    threshold, weight above it, weight at it, #valid, #labels outside [0, C) that are not ignore_index, #above); no host read."""
+    code, param, n_min = _seg_criterion_args(logits, label, kind, gamma, T, n_min)
+    B, IH, IW, C = logits.shape
+    _, OH, OW = label.shape
+    assert label.is_contiguous()
+    L = lib()
+    ws = torch.empty(L.paif_seg_criterion_workspace_words(B, OH, OW), device=logits.device, dtype=torch.int32)
+    planes = torch.empty((2, B, OH, OW), device=logits.device, dtype=torch.float32)
+    coef = torch.empty(8, device=logits.device, dtype=torch.float32)
+    _lib.check(L.paif_seg_criterion_fwd(_p(logits), ctypes.c_void_p(label.data_ptr()), _p(planes[0]), _p(planes[1]),
+                                        ctypes.c_void_p(ws.data_ptr()), _p(coef), code, param, n_min, B, IH, IW, C, OH, OW,
+                                        int(ignore_index), _stream()), "seg_criterion_fwd")
+    return coef, planes[0], planes[1]
+
+
+def seg_criterion_bwd(logits, label, lplane, lse, coef, upstream, kind, gamma=0.0, ignore_index=255):
+    """-> (d value / d logits NHWC [B,IH,IW,cp], the full-resolution buffer [B,OH,OW,cp]); cp = C rounded up to 4, the narrowest pad the
+    adjoint kernel takes; pad channels zero.  upstream: 0-d / 1-element float32 device tensor.  Identity scale: both are one tensor."""
+    B, IH, IW, C = logits.shape
+    _, OH, OW = label.shape
+    cp = (C + 3) // 4 * 4
+    dfull = torch.empty((B, OH, OW, cp), device=logits.device, dtype=torch.float32)
+    _lib.check(lib().paif_seg_criterion_bwd(_p(logits), ctypes.c_void_p(label.data_ptr()), _p(lplane), _p(lse), _p(coef),
+                                            _p(upstream), _p(dfull), SEG_KINDS[kind], float(gamma), B, IH, IW, C, OH, OW,
+                                            int(ignore_index), cp, _stream()), "seg_criterion_bwd")
+    if (IH, IW) == (OH, OW):
+        return dfull, dfull          # the interpolation is the identity, and so is its adjoint
+    return resize_bilinear_adjoint(dfull, 0, cp, IH, IW), dfull
+
+
+class SegCriterion(torch.autograd.Function):
+    """NormalLoss / SoftmaxFocalLoss / OhemCELoss on F.interpolate(seg_map, label.shape[1:], bilinear, align_corners=False) as the fused
+    HIP kernels paif_seg_criterion_fwd / _bwd; differentiable w.r.t. seg_map only."""
+
+    @staticmethod
+    def forward(ctx, seg_map, label, kind, gamma, T, n_min, ignore_index):
+        logits = to_nhwc(seg_map.detach())
+        coef, lplane, lse = seg_criterion_fwd(logits, label, kind, gamma, T, n_min, ignore_index)
+        ctx.save_for_backward(logits, label, coef, lplane, lse)
+        ctx.args = (kind, gamma, ignore_index)
+        return coef[0].clone()
+
+    @staticmethod
+    def backward(ctx, g):
+        logits, label, coef, lplane, lse = ctx.saved_tensors
+        kind, gamma, ignore_index = ctx.args
+        up = g.reshape(1).to(torch.float32).contiguous()
+        d, _ = seg_criterion_bwd(logits, label, lplane, lse, coef, up, kind, gamma, ignore_index)
+        return nhwc_slice_to_nchw(d, logits.shape[-1]), None, None, None, None, None, None
+
+
+def seg_criterion(seg_map, label, kind, gamma=0.0, T=0.0, n_min=0, ignore_index=255):
+    """seg_map [B,C,h,w] (any strides), label int64 [B,H,W], kind "normal" | "focal" | "ohem" -> the criterion's value as a 0-d device
+    tensor (differentiable w.r.t. seg_map).  T = -log(thresh) as a float32 value; C > 32 raises NotImplementedError."""
+    label = label.contiguous()
+    if torch.is_grad_enabled() and seg_map.requires_grad:
+        return SegCriterion.apply(seg_map, label, kind, gamma, T, n_min, ignore_index)
+    return seg_criterion_fwd(to_nhwc(seg_map.detach()), label, kind, gamma, T, n_min, ignore_index)[0][0]
+
+
 _SSIM_WINDOW = {}
 
 
